@@ -10,7 +10,10 @@ scaling).  `value` = Mpixels/s of output, whole job.
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+contract's keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); it measures
+nothing else.  `--dump-outputs DIR` writes what the last step computed as DIR/<name>.npy
+(float32; a fixed, seeded sample of pixels for outputs over 48 MB).  `--full` adds, as one run:
   roofline      the dominant kernel of the headline: algorithmic bytes / hipEvent-timed launch
   modes         both precision modes of the blur as first-class objects, each with its roofline
   resize        BASELINE's other half of the metric: C3, 8192^2 -> 32768^2 Lanczos, float Quantum
@@ -18,6 +21,7 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
                 one roofline object per kernel, and the reference's CPU figure beside each
   sustained     >= 2 s of back-to-back blur calls (power-limit behaviour)
   cpu_baseline  the compiled reference's OpenMP BlurImage on this host (bounded sample)
+  multi_gpu     N > 1: the equalize / c5 / c4 configurations, a few steps each
 
 Other configurations as the step (`--config`): c4 = the batch of 512 images sharded over the
 ranks (strong scaling, no collective), c5 = one 16384^2 image row-sharded over the ranks with
@@ -68,17 +72,25 @@ def parse_args():
                     help="fast: f16x2 products on the matrix cores, f32 accumulation, results within +-1 "
                          "Quantum level of the reference (the tolerance BASELINE.json's north_star states); "
                          "exact: fp64 in the CPU's operation order, bit-identical")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: no modes / resize / configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel records and rooflines, the "
+                         "other modes / resize / configs, the CPU baselines, N > 1: the secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full without modes / resize / configs")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from profiles/pmc_traffic.json instead of two rocprofv3 --pmc passes")
     ap.add_argument("--sustain", type=float, default=2.0, help="seconds of back-to-back calls (0: skip)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N > 1 only: skip the short equalize / c5 / c4 runs reported beside the headline")
+                    help="N > 1, --full: skip the short equalize / c5 / c4 runs reported beside the headline")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for N>1 (nccl = RCCL; gloo rehearses the N>1 control "
                          "flow on a box with fewer GPUs than ranks: ranks then share devices)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------ profiling
@@ -1075,7 +1087,7 @@ def shim_measurements(n, sigma, host):
     import magickcore as mc
     out = {}
     if not mc.available(False):
-        return {"shim": "shim/_build is not built"}
+        return {"shim": "the HIP-backed MagickCore (make -C shim) is not built"}
     before = mc.accelerated_calls()
     source = mc.Image(host)
     source.blur(0.0, sigma).sync()                         # warm-up: library load, tables, pool
@@ -1163,8 +1175,15 @@ def shard_range(total, rank, world):
 
 
 def make_step(im, torch, dist, args, rank, world):
-    """-> (step function, units per step for the whole job, description, scaling)."""
+    """-> (step function, units per step for the whole job, description, scaling, headline image,
+    outputs: () -> {name: device tensor} of what the last step computed)."""
     gen = torch.Generator(device="cuda").manual_seed(42 + rank)
+
+    def reseeded(pixels):
+        # The in-place configurations work on their own results from step to step, and the number of
+        # steps before the dump depends on the clock ramp's timing: refill the source from the seed
+        # (the draw that made it) and run one step, so the dump is a function of the arguments alone.
+        pixels.view(torch.int16).random_(-32768, 32768, generator=torch.Generator(device="cuda").manual_seed(42 + rank))
     if args.config == "c2":
         n = args.size or 8192
         src = random_q16(torch, gen, n, n)
@@ -1178,7 +1197,7 @@ def make_step(im, torch, dist, args, rank, world):
         workload = ("%dx%d RGBA Q16 BlurImage(radius=0,sigma=%g): 79-tap row pass + 79-tap column pass, "
                     "Quantum-rounded intermediate, edge clamp, alpha-weighted colour channels; one "
                     "independent image per GPU (BASELINE configs[1])" % (n, n, args.sigma))
-        return step, float(n) * n * world, workload, "weak", image
+        return step, float(n) * n * world, workload, "weak", image, lambda: {"blur": holder["out"].pixels}
     if args.config == "c4":
         # the batch of 512 independent images, sharded over the ranks: no collective.  A rank keeps a
         # pool of distinct images resident and walks its share of the batch through
@@ -1202,7 +1221,12 @@ def make_step(im, torch, dist, args, rank, world):
             im.batch_images(chain, images, devices=1, streams_per_device=streams)
         workload = ("batch of %d independent %dx%d RGBA Q16 images, sRGB->Lab + ContrastStretch 2%%x1%%, "
                     "sharded over the ranks, MagickHipBatchImages per rank (BASELINE configs[3])" % (batch, k, k))
-        return step, float(batch) * k * k, workload, "strong", None
+
+        def outputs():
+            reseeded(block)
+            step()
+            return {"batch": block}
+        return step, float(batch) * k * k, workload, "strong", None, outputs
     n = args.size or 16384
     lo, hi = shard_range(n, rank, world)
     if args.config == "c5":
@@ -1220,7 +1244,7 @@ def make_step(im, torch, dist, args, rank, world):
             holder["out"] = im.unsharp_mask_image(dilated, 0.0, 10.0, 1.0, 0.02)
         workload = ("%dx%d RGBA Q16 Dilate Disk:15 + UnsharpMask(0x10+1+0.02), row-sharded over the ranks "
                     "with 54 halo rows (BASELINE configs[4])" % (n, n))
-        return step, float(n) * n, workload, "strong", None
+        return step, float(n) * n, workload, "strong", None, lambda: {"unsharp_mask": holder["out"].pixels}
     # equalize: local histogram over the owned rows -> ONE all-reduce of the table (RCCL) -> the
     # identical LUT on every rank -> local apply
     band = random_q16(torch, gen, hi - lo, n)
@@ -1231,7 +1255,38 @@ def make_step(im, torch, dist, args, rank, world):
         D.equalize_band(image, None, total_rows=n)
     workload = ("%dx%d RGBA Q16 EqualizeImage, row-sharded over the ranks, one all-reduce of the "
                 "65536 x 4 table" % (n, n))
-    return step, float(n) * n, workload, "strong", None
+
+    def outputs():
+        reseeded(band)
+        step()
+        return {"equalize": band}
+    return step, float(n) * n, workload, "strong", None, outputs
+
+
+DUMP_BYTES = 48 << 20       # everything a dump writes, values and a sample's pixel indices (under 64 MB)
+
+
+def dump_outputs(torch, directory, outputs):
+    """DIR/<name>.npy, float32, for every output of the last step: the whole [rows, columns, channels]
+    array when all outputs fit in DUMP_BYTES, else [k, channels] for the same seeded sample of k pixels
+    (unique, ascending) with their flat pixel indices in DIR/<name>_pixel_index.npy (float64: exact)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    whole = sum(t.numel() * 4 for t in outputs.values()) <= DUMP_BYTES
+    for name, pixels in outputs.items():
+        channels = pixels.shape[-1]
+        flat = pixels.reshape(-1, channels)
+        if pixels.dtype == torch.uint16:
+            flat = flat.view(torch.int16)
+        if not whole:
+            k = DUMP_BYTES // len(outputs) // (4 * channels + 8)
+            index = np.unique(np.random.default_rng(0).integers(0, flat.shape[0], k))
+            flat = flat[torch.from_numpy(index).to(flat.device)]
+            np.save(os.path.join(directory, name + "_pixel_index.npy"), index.astype(np.float64))
+        if pixels.dtype == torch.uint16:
+            flat = flat.to(torch.int32).bitwise_and(0xFFFF)
+        values = flat.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), values.reshape(pixels.shape) if whole else values)
 
 
 def timed_steps(torch, dist, args, world, step, steps, warmup):
@@ -1271,7 +1326,7 @@ def secondary_distributed(im, torch, dist, args, rank, world):
         sub = copy.copy(args)
         # (MAGICKHIP_BENCH_SECONDARY_SIZE: the image edge, for the two-rank rehearsal of the test suite)
         sub.config, sub.size = config, int(os.environ.get("MAGICKHIP_BENCH_SECONDARY_SIZE", "0"))
-        step, units, workload, scaling, _ = make_step(im, torch, dist, sub, rank, world)
+        step, units, workload, scaling, _, _ = make_step(im, torch, dist, sub, rank, world)
         elapsed, per_rank = timed_steps(torch, dist, sub, world, step, steps, 1)
         out[config] = {"workload": workload, "scaling": scaling, "steps": steps,
                        "ms_per_step": round(elapsed / steps * 1e3, 4),
@@ -1338,7 +1393,7 @@ def main():
     PRECISION_IS_FAST[0] = args.precision == "fast"
     im.set_precision(im.PRECISION_FAST if args.precision == "fast" else im.PRECISION_EXACT)
 
-    step, units, workload, scaling, image = make_step(im, torch, dist, args, rank, world)
+    step, units, workload, scaling, image, outputs = make_step(im, torch, dist, args, rank, world)
 
     # clocks: the chip is idle while the inputs are generated; a few hundred ms of the step bring
     # it to its sustained state before the W warm-up steps the contract counts (MAGICKHIP_BENCH_RAMP=0
@@ -1368,7 +1423,8 @@ def main():
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
-    profile_begin()          # hipEvent pairs around every kernel of the timed steps (async records)
+    if args.full:
+        profile_begin()      # hipEvent pairs around every kernel of the timed steps (async records)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -1377,7 +1433,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    prof = profile_end()
+    prof = profile_end() if args.full else {}       # plain run: no per-kernel records, so no roofline
     per_rank_ms = [elapsed / args.steps * 1e3]
     if distributed:
         mine = torch.tensor([elapsed], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
@@ -1385,12 +1441,19 @@ def main():
         dist.all_gather(every, mine)
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in every]
         elapsed = max(float(t.item()) for t in every)          # the job is as slow as its slowest rank
+    if args.dump_outputs:
+        last = outputs()                    # every rank: an in-place configuration's step may hold a collective
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(torch, args.dump_outputs, last)
+        del last
 
     # N > 1: the configurations with a collective / with row bands, in the same launch.  A watchdog
     # keeps the headline safe: if they do not finish in time rank 0 prints the line without them and
     # every rank leaves (a hung collective must not cost the measurement above).
     secondary = None
-    if distributed and (args.config == "c2") and not args.no_secondary:
+    run_secondary = distributed and args.full and (args.config == "c2") and not args.no_secondary
+    if run_secondary:
         import threading
         done = threading.Event()
         state = {}
@@ -1467,7 +1530,7 @@ def main():
                         roof["hbm_frac"] = roof["frac"]
                         roof["compute_roofline"] = issue
                 result["roofline"] = roof
-            if not args.no_extra and world == 1:
+            if args.full and not args.no_extra and world == 1:
                 result.update(extra_measurements(im, torch, args, image))
                 # BASELINE's metric names two operators; `value` is the one the configuration it is
                 # quoted on (configs[1], the blur) measures — the other half beside it, and the
@@ -1482,7 +1545,7 @@ def main():
                     result["value_exact"] = result["modes"]["exact"]["Mpixels_per_s"]
             result["default_mode"] = ("fast: what an unchanged MagickCore caller gets since round 5 (the library's default; "
                                       "MAGICK_HIP_PRECISION=exact selects the bit-identical mode, `value_exact`)")
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 try:
                     result["cpu_baseline"] = cpu_baseline_blur(args.sigma, im=im, torch=torch)
                     shares = result["cpu_baseline"].pop("identical_share", None) if result["cpu_baseline"] else None
@@ -1501,9 +1564,9 @@ def main():
                                 result.setdefault("extra", {})["cpu_baseline_error"] = entry
                 except Exception as exc:  # the baseline is a report, never a reason to lose the line
                     result["cpu_baseline"] = {"error": str(exc)}
-        else:
+        elif args.full:
             result["kernels_ms"] = {k: round(v["avg_ms"], 4) for k, v in prof.items()}
-    if distributed and (args.config == "c2") and not args.no_secondary:
+    if run_secondary:
         if rank == 0:
             state["line"] = result
         watchdog.start()

@@ -24,9 +24,8 @@ def available(hdri=False):
 
 
 def shim_lib_path(hdri):
-    """MagickCore built with the HIP accelerate backend slotted in (shim/Makefile)."""
-    return os.path.join(os.path.dirname(_HERE), "shim", "_build",
-                        "libMagickCore-hip-%s.so" % ("q16hdri" if hdri else "q16"))
+    """MagickCore built with the HIP accelerate backend slotted in (shim/Makefile puts it in oracle/_ref)."""
+    return os.path.join(_HERE, "_ref", "libMagickCore-hip-%s.so" % ("q16hdri" if hdri else "q16"))
 
 
 def _load(hdri, shim=False):

@@ -1,4 +1,4 @@
-"""ctypes access to the HIP-backed MagickCore build (shim/_build/libMagickCore-hip-*.so): the
+"""ctypes access to the HIP-backed MagickCore build (oracle/_ref/libMagickCore-hip-*.so): the
 reference's MagickCore with shim/accelerate_hip.c + shim/opencl_hip.c slotted in.  bench.py uses it
 to time the drop-in boundary itself — MagickCore's BlurImage / TransformImageColorspace /
 ContrastStretchImage called as an application would call them, pixel caches page-locked by the
@@ -16,7 +16,7 @@ _LIBS = {}
 
 
 def lib_path(hdri=False):
-    return os.path.join(_HERE, "_build", "libMagickCore-hip-%s.so" % ("q16hdri" if hdri else "q16"))
+    return os.path.join(ROOT, "oracle", "_ref", "libMagickCore-hip-%s.so" % ("q16hdri" if hdri else "q16"))
 
 
 def available(hdri=False):

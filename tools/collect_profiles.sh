@@ -1,13 +1,13 @@
 #!/bin/bash
 # Run on the GPU box (through gpurun):   tools/collect_profiles.sh <tag> [quick]
 # Produces under gpurun_out/profiles_<tag>/ (tools/import_profiles.py turns it into profiles/<tag>_*):
-#   stats/, stats_full/   rocprofv3 --kernel-trace --stats of the default bench command
-#                         (headline only / with every secondary config)
+#   stats/, stats_full/   rocprofv3 --kernel-trace --stats of the bench command
+#                         (headline only / --full: with every secondary config)
 #   pmc_<workload>_<fetch|write>/   separate --pmc passes (kernel-trace only) of each workload:
 #                         fast (FAST blur: f16 colour + exact alpha, convolve_fused_hybrid.hip), exact (EXACT
 #                         blur, one launch), hdri (float Quantum blur), resize (C3, FAST: resize_stream.hip), c4, c5
 #   sq_<fast|exact>_<a|b>/  SQ issue / wait / LDS counters of the two fused kernels
-#   bench.json            the bench line of the same box (with cpu_baseline)
+#   bench.json            the --full bench line of the same machine (with cpu_baseline)
 set -u
 TAG=${1:-r6e}
 QUICK=${2:-}
@@ -19,7 +19,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -
   python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra --no-live-traffic > $OUT/stats.log 2>&1
 if [ -z "$QUICK" ]; then
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_full -o bench -- \
-  python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/stats_full.log 2>&1
+  python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/stats_full.log 2>&1
 fi
 workload() {
   case $1 in
@@ -48,5 +48,5 @@ for w in fast exact; do
   timeout 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq_${w}_c -o c -- $(workload $w) > $OUT/sq_${w}_c.log 2>&1
 done
 cd $R
-timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 1500 $OUT/bench.json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """gpurun_out/profiles_<tag>/ (tools/collect_profiles.sh, run on the GPU box) -> the committed files under profiles/:
    <tag>_kernel_stats.csv              rocprofv3 --kernel-trace --stats of the headline command (per kernel)
-   <tag>_kernel_stats_all_configs.csv  the same for the whole default bench command
+   <tag>_kernel_stats_all_configs.csv  the same for the whole `bench.py --full` command
    <tag>_pmc.csv                       per workload and kernel: mean FETCH_SIZE / WRITE_SIZE per launch
    pmc_traffic.json                    HBM bytes per launch, keyed the way bench.py looks them up (FETCH_SIZE is in
                                        KiB and counts half the bytes of a wide coalesced stream on gfx950: x2;
