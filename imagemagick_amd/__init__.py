@@ -20,7 +20,7 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
            "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image",
-           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
+           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
            "logical_device_count", "device_info", "device_count",
@@ -394,6 +394,18 @@ def despeckle_image(image):
     return _pair_operator("MagickHipDespeckleImage", image)
 
 
+def statistic_image(image, statistic, width, height):
+    """StatisticImage(image, type, width, height) — MagickCore/statistic.c:2918.  statistic: a name of
+    the StatisticOptions table (option.c:2183, any case: "Median", "NonPeak", "RMS", ...) or an
+    MhStatisticType value."""
+    if isinstance(statistic, str):
+        key = statistic.lower()
+        if key not in _lib.STATISTICS:
+            raise ValueError("unknown statistic %r" % statistic)
+        statistic = _lib.STATISTICS[key]
+    return _pair_operator("MagickHipStatisticImage", image, int(statistic), int(width), int(height))
+
+
 def local_contrast_image(image, radius, strength):
     """LocalContrastImage(image, radius, strength) — MagickCore/effect.c:1760."""
     return _pair_operator("MagickHipLocalContrastImage", image, radius, strength)
@@ -629,7 +641,8 @@ def apply_histogram(image, hist, intensity_mode, equalize, black_point=0.0, whit
 def _operators(chain):
     """[("colorspace", "Lab"), ("contraststretch", black, white), ("blur", 0, 10), ("morphology",
     "Dilate", 1, "Disk:15"), ("unsharpmask", 0, 10, 1.0, 0.02), ("resize", columns, rows, "Lanczos"),
-    ("equalize",)] -> an MhOperator array (and the byte strings it points at)."""
+    ("equalize",), ("statistic", "Median", width, height)] -> an MhOperator array (and the byte
+    strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):
@@ -645,6 +658,8 @@ def _operators(chain):
             args = [MORPHOLOGY[args[0].lower()], args[1]]
         elif name == "resize":
             args = [args[0], args[1], FILTERS[args[2].lower()] if len(args) > 2 else FILTERS["lanczos"]]
+        elif name == "statistic":
+            args = [_lib.STATISTICS[args[0].lower()] if isinstance(args[0], str) else args[0], args[1], args[2]]
         for k, a in enumerate(args):
             ops[i].args[k] = float(a)
     return ops, keep

@@ -120,7 +120,11 @@ class MhBatchReport(ctypes.Structure):
 
 
 OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morphology": 5,
-             "colorspace": 6, "contraststretch": 7, "equalize": 8}
+             "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9}
+
+# StatisticOptions, MagickCore/option.c:2183 (lower-case keys) -> MhStatisticType
+STATISTICS = {"undefined": 0, "contrast": 10, "gradient": 1, "maximum": 2, "mean": 3, "median": 4,
+              "minimum": 5, "mode": 6, "nonpeak": 7, "rootmeansquare": 8, "rms": 8, "standarddeviation": 9}
 
 
 # every symbol include/magickhip.h declares: (name, restype, argtypes)
@@ -197,6 +201,8 @@ PROTOTYPES = [
                                                     _P(ctypes.c_ssize_t)]),
     ("MagickHipWaveletDenoiseImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double]),
     ("MagickHipDespeckleImage", ctypes.c_int, [_P(MhImage), _P(MhImage)]),
+    ("MagickHipStatisticImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_int, ctypes.c_size_t,
+                                               ctypes.c_size_t]),
     ("MagickHipLocalContrastImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double]),
     ("MagickHipRotationalBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double]),
     ("MagickHipMotionBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double,

@@ -147,6 +147,18 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
             (void) kernels;
             break;
           }
+        case MH_OP_STATISTIC:
+          {
+            // StatisticImage's window reaches H/2 rows up and H-1-H/2 (<= H/2) down
+            // (statistic.c:2979-2981)
+            if (!(p.op.args[1] >= 0.0) || (p.op.args[1] > 65535.0) || !(p.op.args[2] >= 0.0) ||
+                (p.op.args[2] > 65535.0))
+              return fail(MH_BAD_ARGUMENT,"operator %zu: statistic window %gx%g",i,p.op.args[1],p.op.args[2]);
+            const size_t height=(size_t) p.op.args[2];
+            p.reach=(height > 1 ? height : 1)/2;
+            p.stencil=true;
+            break;
+          }
         case MH_OP_RESIZE: case MH_OP_COLORSPACE:
           break;
         case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
@@ -215,6 +227,10 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       break;
     case MH_OP_RESIZE:
       status=MagickHipResizeImage(&cur.image,&next,(MhFilterType) (int) op.args[2]);
+      break;
+    case MH_OP_STATISTIC:
+      status=MagickHipStatisticImage(&cur.image,&next,(MhStatisticType) (int) op.args[0],(size_t) op.args[1],
+        (size_t) op.args[2]);
       break;
     case MH_OP_MORPHOLOGY:
       status=MagickHipMorphologyImage(&cur.image,&next,(MhMorphologyMethod) (int) op.args[0],

@@ -416,6 +416,10 @@ MhStatus launch_rotational_blur(const View &src,const View &dst,const double *co
 MhStatus launch_local_contrast(const View &src,const View &dst,double radius,double strength,
   const Roles &roles);
 MhStatus launch_despeckle(const View &src,const View &dst,const Roles &roles);
+// StatisticImage (statistic.hip): type = MhStatisticType; MH_UNSUPPORTED when the window does not
+// fit the LDS tile (include/magickhip.h)
+MhStatus launch_statistic(const View &src,const View &dst,int type,size_t width,size_t height,
+  const Roles &roles);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

@@ -1080,6 +1080,17 @@ MH_API MhStatus MagickHipDespeckleImage(const MhImage *image,MhImage *despeckle_
   return pair.commit();
 }
 
+MH_API MhStatus MagickHipStatisticImage(const MhImage *image,MhImage *statistic_image,
+  MhStatisticType type,size_t width,size_t height)
+{
+  MH_TRY(gate_pair(image,statistic_image,"StatisticImage",true));
+  Pair pair;
+  MH_TRY(pair.open(image,statistic_image));
+  Roles roles=channel_roles(image,statistic_image);
+  MH_TRY(launch_statistic(pair.src.view,pair.dst.view,(int) type,width,height,roles));
+  return pair.commit();
+}
+
 MH_API MhStatus MagickHipLocalContrastImage(const MhImage *image,MhImage *contrast_image,
   double radius,double strength)
 {

@@ -452,6 +452,32 @@ MH_API MhStatus MagickHipWaveletDenoiseImage(const MhImage *image,MhImage *noise
 /* AccelerateDespeckleImage: DespeckleImage(image), effect.c:1308-1490 (16 Hull sweeps). */
 MH_API MhStatus MagickHipDespeckleImage(const MhImage *image,MhImage *despeckle_image);
 
+/* StatisticType, statistic.h:139-152 (the same values) */
+typedef enum
+{
+  MH_STATISTIC_UNDEFINED = 0,      /* StatisticImage's default branch: the mean */
+  MH_STATISTIC_GRADIENT = 1,
+  MH_STATISTIC_MAXIMUM = 2,
+  MH_STATISTIC_MEAN = 3,
+  MH_STATISTIC_MEDIAN = 4,
+  MH_STATISTIC_MINIMUM = 5,
+  MH_STATISTIC_MODE = 6,
+  MH_STATISTIC_NONPEAK = 7,
+  MH_STATISTIC_ROOT_MEAN_SQUARE = 8,
+  MH_STATISTIC_STANDARD_DEVIATION = 9,
+  MH_STATISTIC_CONTRAST = 10
+} MhStatisticType;
+
+/* AccelerateStatisticImage: StatisticImage(image,type,width,height), statistic.c:2918-3163;
+   bit-identical in both precision modes, Q16 and float Quantum.  Output (x,y) is the statistic
+   of the W x H window from (x-W/2, y-H/2), W = max(width,1), H = max(height,1), edge-clamped.
+   Window limit: one channel of the workgroup's (W+15) x (H+15) window must fit 64 KiB of LDS at
+   2 bytes a sample (median, mode, nonpeak; every type on Q16) or 4 bytes (the other types on
+   float Quantum), i.e. up to 166 x 166 and 113 x 113 for square windows; W and H at most 4096.
+   Larger windows return MH_UNSUPPORTED (the CPU path runs). */
+MH_API MhStatus MagickHipStatisticImage(const MhImage *image,MhImage *statistic_image,
+  MhStatisticType type,size_t width,size_t height);
+
 /* AccelerateLocalContrastImage: LocalContrastImage(image,radius,strength), effect.c:1760-2010.
    MH_UNSUPPORTED (CPU path) when the blur width 0.002*max(columns,rows)*|radius| is 0 or does
    not leave room for the mirrored padding. */
@@ -671,7 +697,8 @@ typedef enum
   MH_OP_MORPHOLOGY = 5,        /* args: MhMorphologyMethod, iterations, bias; text: kernel string */
   MH_OP_COLORSPACE = 6,        /* args: MhColorspace */
   MH_OP_CONTRAST_STRETCH = 7,  /* args: black_point, white_point (pixel counts, enhance.c:1544) */
-  MH_OP_EQUALIZE = 8
+  MH_OP_EQUALIZE = 8,
+  MH_OP_STATISTIC = 9          /* args: MhStatisticType, width, height */
 } MhOperatorKind;
 
 typedef struct MhOperator

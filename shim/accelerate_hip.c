@@ -987,6 +987,29 @@ MagickPrivate Image *AccelerateDespeckleImage(const Image *image,ExceptionInfo *
   return(despeckle_image);
 }
 
+/* StatisticImage's call site (the shim's own hook, shim/patch_hooks.py): statistic.c:2952 */
+MagickPrivate Image *AccelerateStatisticImage(const Image *image,const StatisticType type,
+  const size_t width,const size_t height,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *statistic_image;
+
+  if (IsImageAcceleratable(image) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  if (BeginHipCall(&call,image,image->columns,image->rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  /* StatisticType and MhStatisticType share their values (statistic.h:139-152) */
+  statistic_image=EndHipCall(&call,call.library->StatisticImage(&call.source,&call.destination,
+    (MhStatisticType) type,width,height));
+  if (statistic_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  HipAccepted(image);
+  return(statistic_image);
+}
+
 /* LocalContrastImage's call site: effect.c:1794-1798 */
 MagickPrivate Image *AccelerateLocalContrastImage(const Image *image,const double radius,
   const double strength,ExceptionInfo *exception)

@@ -45,6 +45,7 @@ typedef struct _HipLibrary
     const ptrdiff_t *);
   MhStatus (*WaveletDenoiseImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*DespeckleImage)(const MhImage *,MhImage *);
+  MhStatus (*StatisticImage)(const MhImage *,MhImage *,MhStatisticType,size_t,size_t);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

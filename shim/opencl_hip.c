@@ -174,6 +174,7 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(MotionBlurImageWithKernel,"MagickHipMotionBlurImageWithKernel");
   MH_RESOLVE(WaveletDenoiseImage,"MagickHipWaveletDenoiseImage");
   MH_RESOLVE(DespeckleImage,"MagickHipDespeckleImage");
+  MH_RESOLVE(StatisticImage,"MagickHipStatisticImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Generates, at build time, copies of four MagickCore sources with the accelerate call
+"""Generates, at build time, copies of six MagickCore sources with the accelerate call
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
-ContrastStretch, WaveletDenoise's hook without its softness argument.  Each hook is the reference's own three-line idiom
+ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
+StatisticImage lacks altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -28,6 +29,13 @@ COLORSPACE_PROTOTYPE = '''
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 extern MagickPrivate MagickBooleanType AccelerateTransformImageColorspace(Image *,
   const ColorspaceType,ExceptionInfo *);
+#endif
+'''
+
+STATISTIC_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate Image *AccelerateStatisticImage(const Image *,const StatisticType,
+  const size_t,const size_t,ExceptionInfo *);
 #endif
 '''
 
@@ -102,11 +110,25 @@ def visual_effects(text):
                 "visual-effects.c")
 
 
+def statistic(text):
+    # StatisticImage has no accelerate hook in the reference: one in front of its CloneImage
+    text = after_includes(text, STATISTIC_PROTOTYPE)
+    anchor = "  statistic_image=CloneImage(image,0,0,MagickTrue,\n    exception);\n"
+    hook = '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  statistic_image=AccelerateStatisticImage(image,type,width,height,exception);
+  if (statistic_image != (Image *) NULL)
+    return(statistic_image);
+#endif
+''' + anchor
+    return once(text, anchor, hook, "statistic.c")
+
+
 def main():
     source, out = sys.argv[1], sys.argv[2]
     os.makedirs(out, exist_ok=True)
     for name, fn in (("morphology.c", morphology), ("effect.c", effect), ("enhance.c", enhance),
-                     ("colorspace.c", colorspace), ("visual-effects.c", visual_effects)):
+                     ("colorspace.c", colorspace), ("visual-effects.c", visual_effects),
+                     ("statistic.c", statistic)):
         text = open(os.path.join(source, name), encoding="latin-1").read()
         patched = fn(text)
         with open(os.path.join(out, name), "w", encoding="latin-1") as f:

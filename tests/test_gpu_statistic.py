@@ -1,0 +1,147 @@
+"""StatisticImage (statistic.c:2918-3163) on the device against the compiled reference: every
+type, Q16 and float Quantum, 1-4 channels, both precision modes, bit-identical (float NaNs at the
+same places).  Also the whole-frame cases and the routing between the kernels of statistic.hip."""
+import numpy as np
+import pytest
+
+from conftest import make_pixels, to_device
+from statistic_oracle import TYPES, RANK, ref_statistic, repeated_keys, assert_same
+
+pytestmark = pytest.mark.gpu
+
+Q16, HDRI = np.uint16, np.float32
+WINDOWS = [(0, 0), (2, 2), (3, 3), (4, 1), (1, 6), (5, 5), (7, 3), (15, 15)]
+
+
+def check(im, refmod, px, statistic, width, height, what=""):
+    got = im.statistic_image(im.Image(to_device(px)), statistic, width, height).numpy()
+    want = ref_statistic(refmod, refmod.RefImage(px), statistic, width, height).numpy()
+    assert_same(got, want, "%s %dx%d %s %s" % (statistic, width, height, px.dtype.name, what))
+    return got
+
+
+@pytest.mark.parametrize("channels", [1, 2, 3, 4])
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+@pytest.mark.parametrize("statistic", list(TYPES))
+def test_statistic_windows(im, refmod, statistic, dtype, channels):
+    px = make_pixels(61, 97, channels, dtype, seed=11 + channels)
+    for width, height in WINDOWS:
+        check(im, refmod, px, statistic, width, height, "c%d" % channels)
+
+
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+@pytest.mark.parametrize("statistic", list(TYPES))
+def test_statistic_large_and_oversized_windows(im, refmod, statistic, dtype):
+    """31 x 31 (the selection route for the rank types) and windows larger than the frame, which
+    the edge clamp fills from the frame's border."""
+    px = make_pixels(41, 53, 4, dtype, seed=5)
+    check(im, refmod, px, statistic, 31, 31)
+    small = make_pixels(13, 17, 2, dtype, seed=6)
+    check(im, refmod, small, statistic, 25, 21, "window over the frame")
+    check(im, refmod, small, statistic, 40, 3, "window over the frame")
+
+
+@pytest.mark.parametrize("shape", [(1, 150), (150, 1)])
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+@pytest.mark.parametrize("statistic", list(TYPES))
+def test_statistic_thin_frames(im, refmod, statistic, dtype, shape):
+    px = make_pixels(shape[0], shape[1], 3, dtype, seed=8)
+    for width, height in [(3, 3), (5, 1), (1, 7), (15, 15)]:
+        check(im, refmod, px, statistic, width, height, "frame %dx%d" % (shape[1], shape[0]))
+
+
+@pytest.mark.parametrize("kind", ["binary", "levels"])
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+@pytest.mark.parametrize("window", [(3, 3), (4, 2), (5, 5), (7, 3), (15, 15), (31, 31)])
+def test_rank_statistics_on_repeated_keys(im, refmod, window, dtype, kind):
+    """Random 16-bit data makes the mode the minimum and the nonpeak value the median almost
+    everywhere; on few distinct keys both take their own branches."""
+    px = repeated_keys(47, 59, 2, dtype, kind)
+    got = {s: check(im, refmod, px, s, window[0], window[1], kind) for s in RANK + ("Minimum",)}
+    assert (got["Mode"] != got["Minimum"]).any(), "the mode never left the minimum: the case tests nothing"
+    if kind == "binary":
+        # a window of both keys has its median at one end of the list: nonpeak takes the other
+        assert (got["NonPeak"] != got["Median"]).any()
+
+
+def test_float_keys_outside_the_quantum_range(im, refmod):
+    """ScaleQuantumToShort on float Quantum: NaN and negatives -> 0, 65535 and above -> 65535,
+    the rest rounded with a float add; moments and extremes see the raw samples (NaN included)."""
+    rng = np.random.default_rng(21)
+    px = rng.uniform(-3000.0, 70000.0, (37, 45, 2)).astype(np.float32)
+    px[rng.random(px.shape) < 0.01] = np.nan
+    px[::7, ::5, 0] = np.float32(0.5)                # ties of the f32 rounding
+    px[::9, ::4, 1] = np.float32(65534.5)
+    for statistic in TYPES:
+        for width, height in [(3, 3), (6, 5), (9, 9)]:
+            check(im, refmod, px, statistic, width, height, "wide float range")
+
+
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+def test_statistic_fast_precision_is_bit_identical(im, refmod, dtype):
+    px = make_pixels(45, 70, 4, dtype, seed=31)
+    im.set_precision(im.PRECISION_FAST)
+    try:
+        for statistic in TYPES:
+            for width, height in [(3, 3), (5, 5), (7, 9)]:
+                check(im, refmod, px, statistic, width, height, "FAST")
+    finally:
+        im.set_precision(im.PRECISION_EXACT)
+
+
+def test_statistic_names_and_values(im):
+    px = make_pixels(20, 30, 1, Q16, seed=1)
+    dev = im.Image(to_device(px))
+    a = im.statistic_image(dev, "standarddeviation", 3, 3).numpy()
+    b = im.statistic_image(dev, TYPES["StandardDeviation"], 3, 3).numpy()
+    assert np.array_equal(a, b)
+    assert np.array_equal(im.statistic_image(dev, "RMS", 3, 3).numpy(),
+                          im.statistic_image(dev, "RootMeanSquare", 3, 3).numpy())
+    with pytest.raises(ValueError):
+        im.statistic_image(dev, "Average", 3, 3)
+
+
+@pytest.mark.parametrize("statistic,window", [("Median", 3), ("Median", 5), ("Mean", 9)])
+def test_statistic_whole_frame(im, refmod, statistic, window):
+    """A 2048 x 2048 RGBA Q16 frame, compared on every sample."""
+    px = make_pixels(2048, 2048, 4, Q16, seed=99)
+    check(im, refmod, px, statistic, window, window, "2048^2 RGBA")
+
+
+def test_statistic_host_image(im, refmod):
+    px = make_pixels(33, 64, 4, Q16, seed=3)
+    got = im.statistic_image(im.Image(px.copy()), "Median", 5, 3).numpy()
+    assert_same(got, ref_statistic(refmod, refmod.RefImage(px), "Median", 5, 3).numpy(), "host image")
+
+
+# the kernel each window and type runs (statistic.hip): rank types by n = W*H
+ROUTES = [("Median", (4, 4), "statistic_rank_net16"), ("Mode", (1, 1), "statistic_rank_net16"),
+          ("NonPeak", (17, 1), "statistic_rank_net32"), ("Median", (8, 4), "statistic_rank_net32"),
+          ("Mode", (1, 32), "statistic_rank_net32"), ("Median", (3, 11), "statistic_rank_select"),
+          ("NonPeak", (33, 1), "statistic_rank_select"), ("Mode", (6, 6), "statistic_rank_select"),
+          ("Minimum", (1, 1), "statistic_extreme"), ("Contrast", (9, 9), "statistic_extreme"),
+          ("Mean", (1, 1), "statistic_moment"), ("StandardDeviation", (9, 9), "statistic_moment")]
+
+
+@pytest.mark.parametrize("statistic,window,route", ROUTES)
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+def test_statistic_routes(im, refmod, statistic, window, route, dtype):
+    from imagemagick_amd import _lib
+    import torch
+    lib = _lib.load()
+    px = make_pixels(40, 70, 3, dtype, seed=17)
+    dev = im.Image(to_device(px))
+    lib.MhResetProfileRecords()
+    lib.MhSetProfileEnabled(1)
+    try:
+        got = im.statistic_image(dev, statistic, *window).numpy()
+        torch.cuda.synchronize()
+    finally:
+        lib.MhSetProfileEnabled(0)
+    records = (_lib.MhKernelProfileRecord * 48)()
+    n = lib.MhGetProfileRecords(records, 48)
+    names = {records[i].kernel_name.decode() for i in range(min(n, 48))}
+    lib.MhResetProfileRecords()
+    assert {name for name in names if name.startswith("statistic_")} == {route}, names
+    want = ref_statistic(refmod, refmod.RefImage(px), statistic, *window).numpy()
+    assert_same(got, want, "%s %s via %s" % (statistic, window, route))
