@@ -20,7 +20,7 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
            "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image",
-           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
+           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
            "logical_device_count", "device_info", "device_count",
@@ -406,6 +406,19 @@ def statistic_image(image, statistic, width, height):
     return _pair_operator("MagickHipStatisticImage", image, int(statistic), int(width), int(height))
 
 
+def bilateral_blur_image(image, width, height, intensity_sigma, spatial_sigma):
+    """BilateralBlurImage(image, width, height, intensity_sigma, spatial_sigma) — MagickCore/effect.c:894.
+    max(width,1) and max(height,1) must be odd (MagickHipError UNSUPPORTED otherwise)."""
+    return _pair_operator("MagickHipBilateralBlurImage", image, int(width), int(height), float(intensity_sigma),
+                          float(spatial_sigma))
+
+
+def selective_blur_image(image, radius, sigma, threshold):
+    """SelectiveBlurImage(image, radius, sigma, threshold) — MagickCore/effect.c:3406; threshold in
+    Quantum units."""
+    return _pair_operator("MagickHipSelectiveBlurImage", image, float(radius), float(sigma), float(threshold))
+
+
 def local_contrast_image(image, radius, strength):
     """LocalContrastImage(image, radius, strength) — MagickCore/effect.c:1760."""
     return _pair_operator("MagickHipLocalContrastImage", image, radius, strength)
@@ -641,8 +654,9 @@ def apply_histogram(image, hist, intensity_mode, equalize, black_point=0.0, whit
 def _operators(chain):
     """[("colorspace", "Lab"), ("contraststretch", black, white), ("blur", 0, 10), ("morphology",
     "Dilate", 1, "Disk:15"), ("unsharpmask", 0, 10, 1.0, 0.02), ("resize", columns, rows, "Lanczos"),
-    ("equalize",), ("statistic", "Median", width, height)] -> an MhOperator array (and the byte
-    strings it points at)."""
+    ("equalize",), ("statistic", "Median", width, height), ("bilateralblur", width, height,
+    intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold)] -> an MhOperator
+    array (and the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):

@@ -120,7 +120,8 @@ class MhBatchReport(ctypes.Structure):
 
 
 OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morphology": 5,
-             "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9}
+             "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9,
+             "bilateralblur": 10, "selectiveblur": 11}
 
 # StatisticOptions, MagickCore/option.c:2183 (lower-case keys) -> MhStatisticType
 STATISTICS = {"undefined": 0, "contrast": 10, "gradient": 1, "maximum": 2, "mean": 3, "median": 4,
@@ -203,6 +204,13 @@ PROTOTYPES = [
     ("MagickHipDespeckleImage", ctypes.c_int, [_P(MhImage), _P(MhImage)]),
     ("MagickHipStatisticImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_int, ctypes.c_size_t,
                                                ctypes.c_size_t]),
+    ("MagickHipBilateralBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_size_t, ctypes.c_size_t,
+                                                   ctypes.c_double, ctypes.c_double]),
+    ("MagickHipSelectiveBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double,
+                                                   ctypes.c_double]),
+    ("MhBilateralBlurTables", ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, ctypes.c_double,
+                                             _P(ctypes.c_double), _P(ctypes.c_double)]),
+    ("MhSelectiveBlurKernel", ctypes.c_size_t, [ctypes.c_double, ctypes.c_double, _P(ctypes.c_double)]),
     ("MagickHipLocalContrastImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double]),
     ("MagickHipRotationalBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double]),
     ("MagickHipMotionBlurImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double,

@@ -159,6 +159,22 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
             p.stencil=true;
             break;
           }
+        case MH_OP_BILATERAL_BLUR:
+          {
+            // BilateralBlurImage's window reaches H/2 rows up and down (effect.c:1022)
+            if (!(p.op.args[0] >= 0.0) || (p.op.args[0] > 65535.0) || !(p.op.args[1] >= 0.0) ||
+                (p.op.args[1] > 65535.0))
+              return fail(MH_BAD_ARGUMENT,"operator %zu: bilateral window %gx%g",i,p.op.args[0],p.op.args[1]);
+            const size_t height=(size_t) p.op.args[1];
+            p.reach=(height > 1 ? height : 1)/2;
+            p.stencil=true;
+            break;
+          }
+        case MH_OP_SELECTIVE_BLUR:
+          // SelectiveBlurImage's window is centred (effect.c:3559-3560)
+          p.reach=(MhGetOptimalKernelWidth1D(p.op.args[0],p.op.args[1])-1)/2;
+          p.stencil=true;
+          break;
         case MH_OP_RESIZE: case MH_OP_COLORSPACE:
           break;
         case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
@@ -231,6 +247,13 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
     case MH_OP_STATISTIC:
       status=MagickHipStatisticImage(&cur.image,&next,(MhStatisticType) (int) op.args[0],(size_t) op.args[1],
         (size_t) op.args[2]);
+      break;
+    case MH_OP_BILATERAL_BLUR:
+      status=MagickHipBilateralBlurImage(&cur.image,&next,(size_t) op.args[0],(size_t) op.args[1],op.args[2],
+        op.args[3]);
+      break;
+    case MH_OP_SELECTIVE_BLUR:
+      status=MagickHipSelectiveBlurImage(&cur.image,&next,op.args[0],op.args[1],op.args[2]);
       break;
     case MH_OP_MORPHOLOGY:
       status=MagickHipMorphologyImage(&cur.image,&next,(MhMorphologyMethod) (int) op.args[0],

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <vector>
 #include <strings.h>
 
 namespace {
@@ -1393,10 +1394,70 @@ MhKernelInfo *acquire_emboss_kernel(double radius,double sigma)
   return k;
 }
 
+// BlurGaussian, effect.c:852-856
+static double blur_gaussian(double x,double sigma)
+{
+  return exp(-((double) x*x)*perceptible_reciprocal(2.0*sigma*sigma))*
+    perceptible_reciprocal(k2Pi*sigma*sigma);
+}
+
+// BilateralBlurImage's tables, effect.c:951-952 and :960-970.  intensity_gaussian[d+255] for a
+// difference d of two intensity bytes; the reference leaves entry 510 (d = +255) unwritten, here
+// it continues the series.  spatial_gaussian[v*W+u] for the tap (u-W/2, v-H/2) from the centre.
+void bilateral_blur_tables(size_t width,size_t height,double intensity_sigma,double spatial_sigma,
+  double *intensity_gaussian,double *spatial_gaussian)
+{
+  for (ptrdiff_t w=-255; w <= 255; w++)
+    intensity_gaussian[w+255]=blur_gaussian((double) w,intensity_sigma);
+  intensity_gaussian[511]=0.0;
+  const ptrdiff_t mid_x=(ptrdiff_t) (width/2),mid_y=(ptrdiff_t) (height/2);
+  size_t n=0;
+  for (ptrdiff_t v=0; v < (ptrdiff_t) height; v++)
+    for (ptrdiff_t u=0; u < (ptrdiff_t) width; u++)
+      {
+        // BlurDistance(0,0,u-mid.x,v-mid.y), effect.c:846-850
+        const ptrdiff_t du=u-mid_x,dv=v-mid_y;
+        const double distance=sqrt(((double) 0-du)*((double) 0-du)+((double) 0-dv)*((double) 0-dv));
+        spatial_gaussian[n++]=blur_gaussian(distance,spatial_sigma);
+      }
+}
+
+// SelectiveBlurImage's kernel, effect.c:3456-3466: a Gaussian that is not normalised
+void selective_blur_kernel_values(size_t width,double sigma,double *kernel)
+{
+  const double s=magick_sigma(sigma);
+  const ptrdiff_t j=(ptrdiff_t) (width-1)/2;
+  size_t i=0;
+  for (ptrdiff_t v=-j; v <= j; v++)
+    for (ptrdiff_t u=-j; u <= j; u++)
+      kernel[i++]=(double) (exp(-((double) u*u+v*v)/(2.0*s*s))/(2.0*kPi*s*s));
+}
+
 } // namespace mh
 
 // ===================================================================== C ABI
 extern "C" {
+
+// the host-built tables of the edge-preserving blurs, for inspection
+MH_API MhStatus MhBilateralBlurTables(size_t width,size_t height,double intensity_sigma,double spatial_sigma,
+  double *intensity_gaussian,double *spatial_gaussian)
+{
+  if ((intensity_gaussian == nullptr) || (spatial_gaussian == nullptr))
+    return mh::fail(MH_BAD_ARGUMENT,"MhBilateralBlurTables: null table");
+  const size_t W=width > 1 ? width : 1,H=height > 1 ? height : 1;
+  std::vector<double> intensity(512);
+  mh::bilateral_blur_tables(W,H,intensity_sigma,spatial_sigma,intensity.data(),spatial_gaussian);
+  memcpy(intensity_gaussian,intensity.data(),511*sizeof(double));
+  return MH_OK;
+}
+
+MH_API size_t MhSelectiveBlurKernel(double radius,double sigma,double *kernel)
+{
+  const size_t width=MhGetOptimalKernelWidth1D(radius,sigma);
+  if (kernel != nullptr)
+    mh::selective_blur_kernel_values(width,sigma,kernel);
+  return width;
+}
 
 // GetOptimalKernelWidth1D, gem.c:262-300
 MH_API size_t MhGetOptimalKernelWidth1D(double radius,double sigma)

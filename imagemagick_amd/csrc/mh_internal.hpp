@@ -420,6 +420,16 @@ MhStatus launch_despeckle(const View &src,const View &dst,const Roles &roles);
 // fit the LDS tile (include/magickhip.h)
 MhStatus launch_statistic(const View &src,const View &dst,int type,size_t width,size_t height,
   const Roles &roles);
+// BilateralBlurImage / SelectiveBlurImage (edge_blur.hip); MH_UNSUPPORTED for an even bilateral
+// window side and when the window does not fit the LDS tile (include/magickhip.h)
+MhStatus launch_bilateral_blur(const View &src,const View &dst,size_t width,size_t height,
+  double intensity_sigma,double spatial_sigma,const Roles &roles,const MhImage *desc);
+MhStatus launch_selective_blur(const View &src,const View &dst,double radius,double sigma,double threshold,
+  const Roles &roles,const MhImage *desc);
+// their host-built tables (kernel_info.cpp): intensity_gaussian has 512 entries, 511 of them used
+void bilateral_blur_tables(size_t width,size_t height,double intensity_sigma,double spatial_sigma,
+  double *intensity_gaussian,double *spatial_gaussian);
+void selective_blur_kernel_values(size_t width,double sigma,double *kernel);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

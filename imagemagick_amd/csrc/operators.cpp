@@ -1091,6 +1091,29 @@ MH_API MhStatus MagickHipStatisticImage(const MhImage *image,MhImage *statistic_
   return pair.commit();
 }
 
+MH_API MhStatus MagickHipBilateralBlurImage(const MhImage *image,MhImage *blur_image,size_t width,
+  size_t height,double intensity_sigma,double spatial_sigma)
+{
+  MH_TRY(gate_pair(image,blur_image,"BilateralBlurImage",true));
+  Pair pair;
+  MH_TRY(pair.open(image,blur_image));
+  Roles roles=channel_roles(image,blur_image);
+  MH_TRY(launch_bilateral_blur(pair.src.view,pair.dst.view,width,height,intensity_sigma,spatial_sigma,roles,
+    image));
+  return pair.commit();
+}
+
+MH_API MhStatus MagickHipSelectiveBlurImage(const MhImage *image,MhImage *blur_image,double radius,
+  double sigma,double threshold)
+{
+  MH_TRY(gate_pair(image,blur_image,"SelectiveBlurImage",true));
+  Pair pair;
+  MH_TRY(pair.open(image,blur_image));
+  Roles roles=channel_roles(image,blur_image);
+  MH_TRY(launch_selective_blur(pair.src.view,pair.dst.view,radius,sigma,threshold,roles,image));
+  return pair.commit();
+}
+
 MH_API MhStatus MagickHipLocalContrastImage(const MhImage *image,MhImage *contrast_image,
   double radius,double strength)
 {

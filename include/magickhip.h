@@ -348,6 +348,13 @@ MH_API void MhScaleKernelInfo(MhKernelInfo *kernel,double scaling_factor,unsigne
 /* GetOptimalKernelWidth1D / 2D, gem.c:262,302 */
 MH_API size_t MhGetOptimalKernelWidth1D(double radius,double sigma);
 MH_API size_t MhGetOptimalKernelWidth2D(double radius,double sigma);
+/* The tables the edge-preserving blurs build on the host, for inspection.  Bilateral (effect.c:951-970):
+   intensity_gaussian[511], entry d+255 for a difference d of two intensity bytes, and
+   spatial_gaussian[W*H], W = max(width,1), H = max(height,1).  Selective (effect.c:3456-3466): returns
+   GetOptimalKernelWidth1D(radius,sigma) and, unless kernel is NULL, fills kernel[width*width]. */
+MH_API MhStatus MhBilateralBlurTables(size_t width,size_t height,double intensity_sigma,double spatial_sigma,
+  double *intensity_gaussian,double *spatial_gaussian);
+MH_API size_t MhSelectiveBlurKernel(double radius,double sigma,double *kernel);
 /* Is the 2-D kernel an outer product column[y]*row[x] (to 1e-13 of its largest cell, no NaN
    cells)?  Returns 1 and fills row[width] / column[height] (either may be NULL), else 0.  FAST
    ConvolveImage runs such kernels (Gaussian:RxS, i.e. GaussianBlurImage) as two 1-D passes
@@ -477,6 +484,30 @@ typedef enum
    Larger windows return MH_UNSUPPORTED (the CPU path runs). */
 MH_API MhStatus MagickHipStatisticImage(const MhImage *image,MhImage *statistic_image,
   MhStatisticType type,size_t width,size_t height);
+
+/* BilateralBlurImage(image,width,height,intensity_sigma,spatial_sigma), effect.c:894-1142 (the
+   reference has no accelerate hook for it); bit-identical in both precision modes, Q16 and float
+   Quantum.  W = max(width,1) and H = max(height,1) must be odd: with an even side the reference's
+   reflected walk reads a column and a row outside the window it fetched, and the call returns
+   MH_UNSUPPORTED (the CPU path runs).  One table entry is restated differently on purpose:
+   intensity_gaussian[510], the weight of a tap whose intensity byte is 255 above the centre's, is
+   never written by the reference (an uninitialised stack slot); here it is
+   BlurGaussian(255,intensity_sigma).  Window limit: the workgroup's (W+15) x (H+15) tile, at
+   channels*sizeof(Quantum)+1 bytes a pixel behind a 4 KiB table, must fit 128 KiB of LDS: up to
+   69 x 69 for RGBA float Quantum, 101 x 101 for RGBA Q16; larger windows return MH_UNSUPPORTED.
+   NaN samples are out of scope. */
+MH_API MhStatus MagickHipBilateralBlurImage(const MhImage *image,MhImage *blur_image,
+  size_t width,size_t height,double intensity_sigma,double spatial_sigma);
+
+/* SelectiveBlurImage(image,radius,sigma,threshold), effect.c:3406-3710 (no accelerate hook in the
+   reference either); bit-identical in both precision modes, Q16 and float Quantum.  threshold is
+   in Quantum units (the CLI's percent conversion is the caller's).  Served: gray images and
+   three-colour images in sRGB or linear RGB, with or without alpha; other colourspaces return
+   MH_UNSUPPORTED.  Window limit: the (width+15)^2 tile at channels*sizeof(Quantum)+8 bytes a pixel
+   (+16 with blending alpha) must fit 128 KiB of LDS: up to 49 x 49 for RGBA float Quantum, 57 x 57
+   for RGBA Q16; larger kernels return MH_UNSUPPORTED.  NaN samples are out of scope. */
+MH_API MhStatus MagickHipSelectiveBlurImage(const MhImage *image,MhImage *blur_image,
+  double radius,double sigma,double threshold);
 
 /* AccelerateLocalContrastImage: LocalContrastImage(image,radius,strength), effect.c:1760-2010.
    MH_UNSUPPORTED (CPU path) when the blur width 0.002*max(columns,rows)*|radius| is 0 or does
@@ -698,7 +729,9 @@ typedef enum
   MH_OP_COLORSPACE = 6,        /* args: MhColorspace */
   MH_OP_CONTRAST_STRETCH = 7,  /* args: black_point, white_point (pixel counts, enhance.c:1544) */
   MH_OP_EQUALIZE = 8,
-  MH_OP_STATISTIC = 9          /* args: MhStatisticType, width, height */
+  MH_OP_STATISTIC = 9,         /* args: MhStatisticType, width, height */
+  MH_OP_BILATERAL_BLUR = 10,   /* args: width, height, intensity_sigma, spatial_sigma */
+  MH_OP_SELECTIVE_BLUR = 11    /* args: radius, sigma, threshold */
 } MhOperatorKind;
 
 typedef struct MhOperator

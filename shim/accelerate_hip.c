@@ -1010,6 +1010,55 @@ MagickPrivate Image *AccelerateStatisticImage(const Image *image,const Statistic
   return(statistic_image);
 }
 
+/* BilateralBlurImage's call site (the shim's own hook, shim/patch_hooks.py): effect.c:935 */
+MagickPrivate Image *AccelerateBilateralBlurImage(const Image *image,const size_t width,
+  const size_t height,const double intensity_sigma,const double spatial_sigma,
+  ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *blur_image;
+
+  /* an even side makes the reference read outside its window: the library declines it too */
+  if ((IsImageAcceleratable(image) == MagickFalse) || ((MagickMax(width,1) & 1) == 0) ||
+      ((MagickMax(height,1) & 1) == 0))
+    return(HipDeclined(image,(Image *) NULL));
+  if (BeginHipCall(&call,image,image->columns,image->rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  blur_image=EndHipCall(&call,call.library->BilateralBlurImage(&call.source,&call.destination,
+    width,height,intensity_sigma,spatial_sigma));
+  if (blur_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  blur_image->type=image->type;      /* effect.c:1134 */
+  HipAccepted(image);
+  return(blur_image);
+}
+
+/* SelectiveBlurImage's call site (the shim's own hook, shim/patch_hooks.py): effect.c:3501 */
+MagickPrivate Image *AccelerateSelectiveBlurImage(const Image *image,const double radius,
+  const double sigma,const double threshold,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *blur_image;
+
+  if (IsImageAcceleratable(image) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  if (BeginHipCall(&call,image,image->columns,image->rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  blur_image=EndHipCall(&call,call.library->SelectiveBlurImage(&call.source,&call.destination,
+    radius,sigma,threshold));
+  if (blur_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  blur_image->type=image->type;      /* effect.c:3702 */
+  HipAccepted(image);
+  return(blur_image);
+}
+
 /* LocalContrastImage's call site: effect.c:1794-1798 */
 MagickPrivate Image *AccelerateLocalContrastImage(const Image *image,const double radius,
   const double strength,ExceptionInfo *exception)

@@ -46,6 +46,8 @@ typedef struct _HipLibrary
   MhStatus (*WaveletDenoiseImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*DespeckleImage)(const MhImage *,MhImage *);
   MhStatus (*StatisticImage)(const MhImage *,MhImage *,MhStatisticType,size_t,size_t);
+  MhStatus (*BilateralBlurImage)(const MhImage *,MhImage *,size_t,size_t,double,double);
+  MhStatus (*SelectiveBlurImage)(const MhImage *,MhImage *,double,double,double);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

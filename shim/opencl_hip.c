@@ -175,6 +175,8 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(WaveletDenoiseImage,"MagickHipWaveletDenoiseImage");
   MH_RESOLVE(DespeckleImage,"MagickHipDespeckleImage");
   MH_RESOLVE(StatisticImage,"MagickHipStatisticImage");
+  MH_RESOLVE(BilateralBlurImage,"MagickHipBilateralBlurImage");
+  MH_RESOLVE(SelectiveBlurImage,"MagickHipSelectiveBlurImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

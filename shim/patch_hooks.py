@@ -3,7 +3,7 @@
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
-StatisticImage lacks altogether.  Each hook is the reference's own three-line idiom
+StatisticImage, BilateralBlurImage and SelectiveBlurImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -39,6 +39,15 @@ extern MagickPrivate Image *AccelerateStatisticImage(const Image *,const Statist
 #endif
 '''
 
+EFFECT_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate Image *AccelerateBilateralBlurImage(const Image *,const size_t,const size_t,
+  const double,const double,ExceptionInfo *);
+extern MagickPrivate Image *AccelerateSelectiveBlurImage(const Image *,const double,const double,
+  const double,ExceptionInfo *);
+#endif
+'''
+
 
 def once(text, anchor, replacement, name):
     if text.count(anchor) != 1:
@@ -52,6 +61,13 @@ def after_includes(text, prototype):
     last = text.rindex(marker, 0, text.index("\n/*\n", text.index(marker)))
     end = text.index("\n", last) + 1
     return text[:end] + prototype + text[end:]
+
+
+def in_function(text, opening, anchor, replacement, name):
+    """once(), within the function that `opening` starts."""
+    begin = text.index(opening)
+    end = text.index("\n}\n", begin)
+    return text[:begin] + once(text[begin:end], anchor, replacement, name) + text[end:]
 
 
 def morphology(text):
@@ -72,7 +88,27 @@ def morphology(text):
 def effect(text):
     text = once(text, "/* This kernel appears to be broken.\n#if defined(MAGICKCORE_OPENCL_SUPPORT)\n  unsharp_image=AccelerateUnsharpMaskImage(",
                 "#if defined(MAGICKCORE_OPENCL_SUPPORT)\n  unsharp_image=AccelerateUnsharpMaskImage(", "effect.c")
-    return once(text, "    return(unsharp_image);\n#endif\n*/\n", "    return(unsharp_image);\n#endif\n", "effect.c")
+    text = once(text, "    return(unsharp_image);\n#endif\n*/\n", "    return(unsharp_image);\n#endif\n", "effect.c")
+    # BilateralBlurImage and SelectiveBlurImage have no accelerate hook in the reference: one in
+    # front of the first CloneImage of each (SelectiveBlurImage owns its kernel by then)
+    text = after_includes(text, EFFECT_PROTOTYPE)
+    anchor = "  blur_image=CloneImage(image,0,0,MagickTrue,exception);\n"
+    text = in_function(text, "MagickExport Image *BilateralBlurImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  blur_image=AccelerateBilateralBlurImage(image,width,height,intensity_sigma,
+    spatial_sigma,exception);
+  if (blur_image != (Image *) NULL)
+    return(blur_image);
+#endif
+''' + anchor, "effect.c")
+    return in_function(text, "MagickExport Image *SelectiveBlurImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  blur_image=AccelerateSelectiveBlurImage(image,radius,sigma,threshold,exception);
+  if (blur_image != (Image *) NULL)
+    {
+      kernel=(MagickRealType *) RelinquishAlignedMemory(kernel);
+      return(blur_image);
+    }
+#endif
+''' + anchor, "effect.c")
 
 
 def enhance(text):
