@@ -137,8 +137,16 @@ def check(name, got, want, limit, detail):
 # Quantum type: the fused fp64 kernel, 14 ResizeImage: whole-number enlargements (one launch on the vector
 # pipe under FAST), other enlargements (matrix pipe), reductions and mixed geometries, Q16 and float,
 # alpha-weighted or four plain channels, both modes, 15 FAST BlurImage / GaussianBlurImage / UnsharpMaskImage on
-# every layout: gray, gray + alpha, RGB, RGBA, four plain channels)
-NUMBER_OF_OPS = 16
+# every layout: gray, gray + alpha, RGB, RGBA, four plain channels, 16 the pointwise enhance operators (FunctionImage,
+# ContrastImage, ModulateImage, GrayscaleImage) with random parameters, colourspace and channel mask, 17 MotionBlurImage /
+# RotationalBlurImage on every layout, alpha kind and shapes from 1 to 600 per side, 18 LocalContrastImage / DespeckleImage /
+# WaveletDenoiseImage on shapes from 33 to 600 per side; 16 to 18 draw both Quantum types)
+NUMBER_OF_OPS = 19
+
+# families 16 to 18: cases the library declined / cases run, per family.  A declined case passes only when the decline
+# condition stated in morphology.hip holds for it, and at most a quarter of a family's cases may be declined.
+declined = {}
+drawn = {}
 
 
 def blur_radius(sigma):
@@ -150,16 +158,124 @@ def blur_radius(sigma):
     return float(np.ceil(rng.uniform(1.0, min(40.0, 6.0 * sigma + 4.0))))
 
 
-def run_case(op=None):
-    """One random case of operator family `op` (None: any); returns the number of mismatches (0 or 1)."""
-    failures = 0
+def draw_frame():
+    """The frame every case starts from (families 16 to 18 draw their own after it)."""
     rows, cols = int(rng.integers(1, 260)), int(rng.integers(1, 330))
     if rng.random() < 0.2:
         rows, cols = int(rng.integers(1, 40)), int(rng.integers(300, 1400))
     kind = int(rng.integers(0, 6))
-    px = pixels(rows, cols, kind)
+    return rows, cols, kind, pixels(rows, cols, kind)
+
+
+def enhance_frame(rows, cols, channels, is_float, kind):
+    frame = float_pixels(rows, cols, kind) if is_float else pixels(rows, cols, kind)
+    return np.ascontiguousarray(frame[:, :, 4 - channels:] if channels == 2 else frame[:, :, :channels])
+
+
+def draw_enhance_case(op):
+    """The inputs of one case of family 16, 17 or 18, drawn without touching the GPU (tests/test_enhance_edge_sizes.py
+    draws a few hundred to check the share of declined cases); "declines": the library's stated condition holds."""
+    case = {"op": op, "float": bool(rng.random() < 0.5), "kind": int(rng.integers(0, 6)), "declines": False,
+            "mask": None, "copy": (), "colorspace": "sRGB", "libm": False}
+    if op == 16:
+        rows, cols = int(rng.integers(1, 260)), int(rng.integers(1, 330))
+        channels = 4 if rng.random() < 0.6 else 3
+        which = int(rng.integers(0, 4))
+        if which == 0:
+            function = ["Polynomial", "Sinusoid", "Arcsin", "Arctan"][int(rng.integers(0, 4))]
+            count = int(rng.integers(1, 5))
+            params = tuple(float(v) for v in rng.uniform(-1.5, 1.5, count)) if function == "Polynomial" else \
+                tuple(float(v) for v in (rng.uniform(0.2, 5.0), rng.uniform(-180.0, 180.0) if function == "Sinusoid" else rng.uniform(0.0, 1.0),
+                                         rng.uniform(0.1, 1.0), rng.uniform(0.0, 1.0))[:count])
+            case.update(name="function", args=(function, params), libm=function != "Polynomial")
+        elif which == 1:
+            case.update(name="contrast", args=(bool(rng.random() < 0.5),), libm=True)
+        elif which == 2:
+            # percentages off the multiples of ten (those put results on exact rounding ties, test_modulate_colour_models)
+            percent = tuple(float(v) for v in np.round(rng.uniform(3.0, 197.0, 3), 3))
+            percent = tuple(v + 0.377 if v % 10.0 == 0.0 else v for v in percent)
+            case.update(name="modulate", args=percent + (["HSL", "HSB"][int(rng.integers(0, 2))],))
+        else:
+            method = ["Rec709Luma", "Rec601Luma", "Rec709Luminance", "Rec601Luminance", "Average", "Brightness", "Lightness",
+                      "MS", "RMS"][int(rng.integers(0, 9))]
+            case.update(name="grayscale", args=(method,), colorspace=["sRGB", "RGB"][int(rng.integers(0, 2))])
+        if rng.random() < 0.5:
+            letters = "RGBA"[:channels]
+            keep = [c for c in range(channels) if rng.random() < 0.5] or [int(rng.integers(0, channels))]
+            case.update(mask="".join(letters[c] for c in keep), copy=tuple(c for c in range(channels) if c not in keep))
+    elif op == 17:
+        rows, cols = int(rng.integers(1, 601)), int(rng.integers(1, 601))
+        channels = int(rng.integers(1, 5))
+        if rng.random() < 0.5:
+            sigma = float(rng.uniform(0.3, 8.0))
+            radius = 0.0 if rng.random() < 0.6 else float(np.ceil(rng.uniform(1.0, 3.0 * sigma + 2.0)))
+            case.update(name="motion_blur", args=(radius, sigma, float(rng.uniform(-360.0, 360.0))))
+        else:
+            # (small angles often: the sample count grows with the angle and the reference's CPU time with it)
+            angle = float(rng.uniform(-360.0, 360.0)) if rng.random() < 0.3 else float(rng.uniform(-20.0, 20.0))
+            case.update(name="rotational_blur", args=(angle,))
+    else:
+        rows, cols = int(rng.integers(33, 601)), int(rng.integers(33, 601))
+        channels = int(rng.integers(1, 5))
+        which = int(rng.integers(0, 3))
+        if which == 0:
+            # a blur width from below 1 (declined) to a little above half the columns (declined from (columns-2)/2 on)
+            longest = max(rows, cols)
+            radius = float(rng.uniform(0.7, 0.55 * cols)) / (0.002 * longest) * (1.0 if rng.random() < 0.8 else -1.0)
+            w = int(longest * 0.002 * abs(radius))                   # launch_local_contrast, morphology.hip
+            case.update(name="local_contrast", args=(radius, float(rng.uniform(-100.0, 100.0))),
+                        declines=(w < 1) or (cols <= 2 * w + 2))
+        elif which == 1:
+            case.update(name="despeckle", args=())
+        else:
+            case.update(name="wavelet_denoise", args=(float(rng.uniform(50.0, 12000.0)), float(rng.uniform(0.0, 1.0))),
+                        declines=(rows < 33) or (cols < 33))              # launch_wavelet_denoise
+    case["frame"] = enhance_frame(rows, cols, channels, case["float"], case["kind"])
+    drawn[op] = drawn.get(op, 0) + 1
+    if case["declines"]:
+        declined[op] = declined.get(op, 0) + 1
+    return case
+
+
+def run_enhance_case(case):
+    """Families 16 to 18 against the compiled reference: bit-identical; where the device's sin / asin / atan is involved
+    Q16 within one level and float within one ULP."""
+    frame, name, args, op = case["frame"], case["name"], case["args"], case["op"]
+    what = "%s %s %dx%dx%d kind %d mask %s %s" % (args, frame.dtype.name, frame.shape[0], frame.shape[1], frame.shape[2],
+                                                  case["kind"], case["mask"], case["colorspace"])
+    reference = refmod.RefImage(frame, case["colorspace"])
+    if case["mask"]:
+        reference.set_channel_mask(case["mask"])
+    image = (dev_float if case["float"] else dev)(frame, colorspace=case["colorspace"], copy_channels=case["copy"])
+    try:
+        got = getattr(im, name + "_image")(image, *args).numpy()
+    except im.MagickHipError as error:
+        if case["declines"] and 4 * declined[op] <= max(drawn[op], 12):
+            return 0
+        print("MISMATCH %s %s: declined (%s); stated condition holds: %s, %d of %d cases declined" % (
+            name, what, error, case["declines"], declined.get(op, 0), drawn[op]), flush=True)
+        return 1
+    if case["declines"]:
+        print("MISMATCH %s %s: the stated decline condition holds and the call went through" % (name, what), flush=True)
+        return 1
+    want = getattr(reference, name)(*args).numpy()
+    if name == "grayscale":                     # the reference re-lays the frame out as gray[+alpha]; ours keeps G and B
+        keep = [0] + ([frame.shape[2] - 1] if frame.shape[2] == 4 else [])
+        got, want = np.ascontiguousarray(got[:, :, keep]), np.ascontiguousarray(want.reshape(frame.shape[0], frame.shape[1], -1)[:, :, [0, -1][:len(keep)]])
+    got = got.reshape(want.shape)
+    if case["float"]:
+        return check_ulp(name, got, want, 1, what) if case["libm"] else check_bits(name, got, want, what)
+    return check(name, got, want, 1 if case["libm"] else 0, what)
+
+
+def run_case(op=None):
+    """One random case of operator family `op` (None: any); returns the number of mismatches (0 or 1)."""
+    failures = 0
+    rows, cols, kind, px = draw_frame()
     if op is None:
-        op = int(rng.integers(0, 16))
+        op = int(rng.integers(0, NUMBER_OF_OPS))
+    if op >= 16:
+        return run_enhance_case(draw_enhance_case(op))
     detail = "%dx%d kind %d" % (rows, cols, kind)
     ref = refmod.RefImage(px)
     if op == 0:                                    # FAST blur, every kernel length of the fused launch

@@ -21,7 +21,7 @@ def stress(im, refmod):
     im.set_precision(im.PRECISION_EXACT)
 
 
-@pytest.mark.parametrize("op", range(16))
+@pytest.mark.parametrize("op", range(19))
 def test_stress_family(stress, im, op):
     assert op < stress.NUMBER_OF_OPS
     stress.setup(6000 + op)
@@ -38,4 +38,4 @@ def test_stress_family(stress, im, op):
 
 def test_stress_families_are_all_covered(stress):
     """The parametrisation above names every family the driver knows."""
-    assert stress.NUMBER_OF_OPS == 16
+    assert stress.NUMBER_OF_OPS == 19
