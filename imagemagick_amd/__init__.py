@@ -20,7 +20,7 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
            "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image",
-           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
+           "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "kuwahara_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
            "logical_device_count", "device_info", "device_count",
@@ -419,6 +419,12 @@ def selective_blur_image(image, radius, sigma, threshold):
     return _pair_operator("MagickHipSelectiveBlurImage", image, float(radius), float(sigma), float(threshold))
 
 
+def kuwahara_image(image, radius, sigma):
+    """KuwaharaImage(image, radius, sigma) — MagickCore/effect.c:1775.  Bit-identical in both
+    precision modes: the operator's own blur always runs as the exact one."""
+    return _pair_operator("MagickHipKuwaharaImage", image, float(radius), float(sigma))
+
+
 def local_contrast_image(image, radius, strength):
     """LocalContrastImage(image, radius, strength) — MagickCore/effect.c:1760."""
     return _pair_operator("MagickHipLocalContrastImage", image, radius, strength)
@@ -655,8 +661,8 @@ def _operators(chain):
     """[("colorspace", "Lab"), ("contraststretch", black, white), ("blur", 0, 10), ("morphology",
     "Dilate", 1, "Disk:15"), ("unsharpmask", 0, 10, 1.0, 0.02), ("resize", columns, rows, "Lanczos"),
     ("equalize",), ("statistic", "Median", width, height), ("bilateralblur", width, height,
-    intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold)] -> an MhOperator
-    array (and the byte strings it points at)."""
+    intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold), ("kuwahara",
+    radius, sigma)] -> an MhOperator array (and the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):

@@ -175,6 +175,16 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
           p.reach=(MhGetOptimalKernelWidth1D(p.op.args[0],p.op.args[1])-1)/2;
           p.stencil=true;
           break;
+        case MH_OP_KUWAHARA:
+          {
+            // the blur's half width plus the selection's: a window reaches width-1 rows up or down, the
+            // interpolation width/2+1 rows down (effect.c:1809-1810, :1893-1951)
+            if (!(p.op.args[0] >= 0.0) || (p.op.args[0] > 65535.0))
+              return fail(MH_BAD_ARGUMENT,"operator %zu: kuwahara radius %g",i,p.op.args[0]);
+            p.reach=(MhGetOptimalKernelWidth1D(p.op.args[0],p.op.args[1])-1)/2+((size_t) p.op.args[0]+1);
+            p.stencil=true;
+            break;
+          }
         case MH_OP_RESIZE: case MH_OP_COLORSPACE:
           break;
         case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
@@ -254,6 +264,9 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       break;
     case MH_OP_SELECTIVE_BLUR:
       status=MagickHipSelectiveBlurImage(&cur.image,&next,op.args[0],op.args[1],op.args[2]);
+      break;
+    case MH_OP_KUWAHARA:
+      status=MagickHipKuwaharaImage(&cur.image,&next,op.args[0],op.args[1]);
       break;
     case MH_OP_MORPHOLOGY:
       status=MagickHipMorphologyImage(&cur.image,&next,(MhMorphologyMethod) (int) op.args[0],

@@ -430,6 +430,13 @@ MhStatus launch_selective_blur(const View &src,const View &dst,double radius,dou
 void bilateral_blur_tables(size_t width,size_t height,double intensity_sigma,double spatial_sigma,
   double *intensity_gaussian,double *spatial_gaussian);
 void selective_blur_kernel_values(size_t width,double sigma,double *kernel);
+// KuwaharaImage behind its BlurImage (kuwahara.hip): blurred = the bit-identical BlurImage of the
+// source, original = the source itself (read only for channels without a trait).  kuwahara_check:
+// what launch_kuwahara would decline (MH_UNSUPPORTED: the window does not fit the LDS tile), asked
+// before the blur is run
+MhStatus kuwahara_check(const View &src,double radius);
+MhStatus launch_kuwahara(const View &blurred,const View &original,const View &dst,double radius,
+  const MhImage *image,const MhImage *kuwahara_image);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

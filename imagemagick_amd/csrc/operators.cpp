@@ -1114,6 +1114,32 @@ MH_API MhStatus MagickHipSelectiveBlurImage(const MhImage *image,MhImage *blur_i
   return pair.commit();
 }
 
+MH_API MhStatus MagickHipKuwaharaImage(const MhImage *image,MhImage *kuwahara_image,double radius,
+  double sigma)
+{
+  MH_TRY(gate_pair(image,kuwahara_image,"KuwaharaImage",true));
+  Pair pair;
+  MH_TRY(pair.open(image,kuwahara_image));
+  const View &src=pair.src.view;
+  MH_TRY(kuwahara_check(src,radius));
+  // gaussian_image=BlurImage(image,radius,sigma), effect.c:1810, always the bit-identical one: the
+  // selection behind it is discrete, and a blur that is one level off can flip it
+  Temp blurred_memory;
+  MH_TRY(blurred_memory.alloc(src.device,src.bytes(),src.stream));
+  MhImage source=*image,blurred=*image;
+  source.pixels=src.pixels;
+  blurred.pixels=blurred_memory.ptr;
+  source.memory=blurred.memory=MH_MEMORY_DEVICE;
+  source.device=blurred.device=src.device;
+  source.stream=blurred.stream=(void *) src.stream;
+  source.precision=blurred.precision=MH_IMAGE_PRECISION(MH_PRECISION_EXACT);
+  MH_TRY(MagickHipBlurImage(&source,&blurred,radius,sigma));
+  View blurred_view=src;
+  blurred_view.pixels=blurred_memory.ptr;
+  MH_TRY(launch_kuwahara(blurred_view,src,pair.dst.view,radius,image,kuwahara_image));
+  return pair.commit();
+}
+
 MH_API MhStatus MagickHipLocalContrastImage(const MhImage *image,MhImage *contrast_image,
   double radius,double strength)
 {

@@ -509,6 +509,21 @@ MH_API MhStatus MagickHipBilateralBlurImage(const MhImage *image,MhImage *blur_i
 MH_API MhStatus MagickHipSelectiveBlurImage(const MhImage *image,MhImage *blur_image,
   double radius,double sigma,double threshold);
 
+/* KuwaharaImage(image,radius,sigma), effect.c:1775-1978 (no accelerate hook in the reference);
+   bit-identical in both precision modes, Q16 and float Quantum, 1-4 channels.  The operator's own
+   BlurImage(image,radius,sigma) always runs as the bit-identical one, whatever MhImage::precision or
+   MhSetPrecision say: the selection behind it is discrete (the quadrant of least luma variance,
+   strict <), so a blur that is one level off can move the result by any amount.  What
+   MagickHipBlurImage declines for (radius,sigma), this call declines too.  Restated: the default
+   interpolation (the bilinear branch of InterpolatePixelChannels, every channel, alpha-weighted where
+   the channel's trait carries Blend) and edge virtual pixels.  Window limit, w = (size_t) radius+1:
+   the workgroup's (14+2w)^2 tile (15+2w for w <= 2) at channels*sizeof(Quantum)+8 bytes a pixel plus
+   8*(15+w)^2 bytes of variances must fit 128 KiB of LDS: radius < 27 for RGBA float Quantum,
+   radius < 34 for RGBA Q16; larger radii (and negative ones) return MH_UNSUPPORTED with the
+   destination untouched.  NaN and infinite samples are out of scope. */
+MH_API MhStatus MagickHipKuwaharaImage(const MhImage *image,MhImage *kuwahara_image,
+  double radius,double sigma);
+
 /* AccelerateLocalContrastImage: LocalContrastImage(image,radius,strength), effect.c:1760-2010.
    MH_UNSUPPORTED (CPU path) when the blur width 0.002*max(columns,rows)*|radius| is 0 or does
    not leave room for the mirrored padding. */
@@ -731,7 +746,8 @@ typedef enum
   MH_OP_EQUALIZE = 8,
   MH_OP_STATISTIC = 9,         /* args: MhStatisticType, width, height */
   MH_OP_BILATERAL_BLUR = 10,   /* args: width, height, intensity_sigma, spatial_sigma */
-  MH_OP_SELECTIVE_BLUR = 11    /* args: radius, sigma, threshold */
+  MH_OP_SELECTIVE_BLUR = 11,   /* args: radius, sigma, threshold */
+  MH_OP_KUWAHARA = 12          /* args: radius, sigma */
 } MhOperatorKind;
 
 typedef struct MhOperator

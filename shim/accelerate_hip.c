@@ -529,6 +529,16 @@ static MagickBooleanType HasMorphologyArtifacts(const Image *image)
 }
 
 /* ------------------------------------------------------------- operators */
+/*
+  Set by AccelerateKuwaharaImage when it declines: KuwaharaImage's CPU code then starts with
+  BlurImage (effect.c:1810) on this thread, and that one call stays on the CPU too - past this
+  hook and past the one in the MorphologyApply its ConvolveImage ends in, which clears the mark.
+  The operator picks a quadrant by a strict comparison of variances of the blurred frame, so behind
+  a blur that is within one level (the default mode's) its result is not the CPU's.
+*/
+static __thread MagickBooleanType
+  kuwahara_blur_on_cpu = MagickFalse;
+
 MagickPrivate Image *AccelerateBlurImage(const Image *image,const double radius,
   const double sigma,ExceptionInfo *exception)
 {
@@ -540,6 +550,8 @@ MagickPrivate Image *AccelerateBlurImage(const Image *image,const double radius,
 
   assert(image != NULL);
   assert(exception != (ExceptionInfo *) NULL);
+  if (kuwahara_blur_on_cpu != MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
   if ((IsImageAcceleratable(image) == MagickFalse) || (HasMorphologyArtifacts(image) != MagickFalse))
     return(HipDeclined(image,(Image *) NULL));
   if (BeginHipStencilCall(&call,image,exception) == MagickFalse)
@@ -762,6 +774,11 @@ MagickPrivate Image *AccelerateMorphologyApply(const Image *image,
   size_t
     n;
 
+  if (kuwahara_blur_on_cpu != MagickFalse)
+    {
+      kuwahara_blur_on_cpu=MagickFalse;      /* the BlurImage of a declined KuwaharaImage */
+      return(HipDeclined(image,(Image *) NULL));
+    }
   /* the user's morphology:compose (morphology.c:4206): the operators the backend composes with */
   switch (compose)
   {
@@ -1057,6 +1074,35 @@ MagickPrivate Image *AccelerateSelectiveBlurImage(const Image *image,const doubl
   blur_image->type=image->type;      /* effect.c:3702 */
   HipAccepted(image);
   return(blur_image);
+}
+
+/* KuwaharaImage's call site (the shim's own hook, shim/patch_hooks.py): effect.c:1810 */
+MagickPrivate Image *AccelerateKuwaharaImage(const Image *image,const double radius,
+  const double sigma,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *kuwahara_image;
+
+  /* the library restates the default interpolation, the bilinear branch of
+     InterpolatePixelChannels (pixel.c:4975-5033), on edge virtual pixels (the gate's); declined
+     calls keep their BlurImage on the CPU as well (kuwahara_blur_on_cpu) */
+  kuwahara_blur_on_cpu=MagickTrue;
+  if ((IsImageAcceleratable(image) == MagickFalse) || (HasMorphologyArtifacts(image) != MagickFalse) ||
+      ((image->interpolate != UndefinedInterpolatePixel) &&
+       (image->interpolate != BilinearInterpolatePixel)))
+    return(HipDeclined(image,(Image *) NULL));
+  if (BeginHipCall(&call,image,image->columns,image->rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  kuwahara_image=EndHipCall(&call,call.library->KuwaharaImage(&call.source,&call.destination,
+    radius,sigma));
+  if (kuwahara_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  kuwahara_blur_on_cpu=MagickFalse;
+  HipAccepted(image);
+  return(kuwahara_image);
 }
 
 /* LocalContrastImage's call site: effect.c:1794-1798 */

@@ -48,6 +48,7 @@ typedef struct _HipLibrary
   MhStatus (*StatisticImage)(const MhImage *,MhImage *,MhStatisticType,size_t,size_t);
   MhStatus (*BilateralBlurImage)(const MhImage *,MhImage *,size_t,size_t,double,double);
   MhStatus (*SelectiveBlurImage)(const MhImage *,MhImage *,double,double,double);
+  MhStatus (*KuwaharaImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

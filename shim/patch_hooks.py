@@ -3,7 +3,7 @@
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
-StatisticImage, BilateralBlurImage and SelectiveBlurImage lack altogether.  Each hook is the reference's own three-line idiom
+StatisticImage, BilateralBlurImage, SelectiveBlurImage and KuwaharaImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -45,6 +45,8 @@ extern MagickPrivate Image *AccelerateBilateralBlurImage(const Image *,const siz
   const double,const double,ExceptionInfo *);
 extern MagickPrivate Image *AccelerateSelectiveBlurImage(const Image *,const double,const double,
   const double,ExceptionInfo *);
+extern MagickPrivate Image *AccelerateKuwaharaImage(const Image *,const double,const double,
+  ExceptionInfo *);
 #endif
 '''
 
@@ -100,13 +102,22 @@ def effect(text):
     return(blur_image);
 #endif
 ''' + anchor, "effect.c")
-    return in_function(text, "MagickExport Image *SelectiveBlurImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+    text = in_function(text, "MagickExport Image *SelectiveBlurImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
   blur_image=AccelerateSelectiveBlurImage(image,radius,sigma,threshold,exception);
   if (blur_image != (Image *) NULL)
     {
       kernel=(MagickRealType *) RelinquishAlignedMemory(kernel);
       return(blur_image);
     }
+#endif
+''' + anchor, "effect.c")
+    # KuwaharaImage has none either: one in front of its BlurImage, so that the whole operator, blur
+    # included, runs on the device
+    anchor = "  gaussian_image=BlurImage(image,radius,sigma,exception);\n"
+    return in_function(text, "MagickExport Image *KuwaharaImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  kuwahara_image=AccelerateKuwaharaImage(image,radius,sigma,exception);
+  if (kuwahara_image != (Image *) NULL)
+    return(kuwahara_image);
 #endif
 ''' + anchor, "effect.c")
 
