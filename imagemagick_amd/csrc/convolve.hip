@@ -19,6 +19,7 @@
 // one-slot-per-R padding that makes the stride-R reads bank-conflict free.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 #include "tie_check.hpp"
 #include "separable_args.hpp"
 #include <cstdlib>
@@ -2168,23 +2169,10 @@ MhStatus launch_separable_folded(const View &src,const SeparableArgs &sep,const 
 {
   if ((horizontal.ntaps < 3) || (vertical.ntaps < 3))
     return fail(MH_BAD_ARGUMENT,"folded separable passes: %d x %d taps",horizontal.ntaps,vertical.ntaps);
-#define MH_LAYOUT(QT) \
-  switch (src.channels) \
-  { \
-    case 1: return launch_folded<QT,1,false>(src,sep,horizontal,vertical); \
-    case 2: return blend ? launch_folded<QT,2,true>(src,sep,horizontal,vertical) : \
-      launch_folded<QT,2,false>(src,sep,horizontal,vertical); \
-    case 3: return launch_folded<QT,3,false>(src,sep,horizontal,vertical); \
-    case 4: return blend ? launch_folded<QT,4,true>(src,sep,horizontal,vertical) : \
-      launch_folded<QT,4,false>(src,sep,horizontal,vertical); \
-    default: break; \
-  }
-  if (src.quantum != MH_QUANTUM_U16)
-    { MH_LAYOUT(float) }
-  else
-    { MH_LAYOUT(uint16_t) }
-#undef MH_LAYOUT
-  return fail(MH_UNSUPPORTED,"%d channels",src.channels);
+  if ((src.channels < 1) || (src.channels > 4))
+    return fail(MH_UNSUPPORTED,"%d channels",src.channels);
+  return dispatch_layout_blend(src.quantum,src.channels,blend,[&](auto L) {
+    return launch_folded<typename decltype(L)::Q,L.C,L.BLEND>(src,sep,horizontal,vertical); });
 }
 
 // ---------------------------------------------------------------- launcher

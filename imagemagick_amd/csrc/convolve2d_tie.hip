@@ -26,6 +26,7 @@
 // here), the fp64 pipe is the bound: 16384^2 x 4 x 709 FMAs = 19 ms at 64 a clock and CU.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 #include "tie_check.hpp"
 #include <vector>
 #include <cmath>
@@ -388,18 +389,8 @@ MhStatus launch_conv2d_tie(const View &src,const View &dst,const MhKernelInfo *k
       args.recomputed=g_tie2d_recomputed[src.device];
     }
   *handled=true;
-#define MH_LAYOUT(QT) \
-  switch (src.channels) \
-  { \
-    case 1: return launch_conv2d_tie_typed<QT,1,false>(src,args,lds); \
-    case 2: return blend ? launch_conv2d_tie_typed<QT,2,true>(src,args,lds) : launch_conv2d_tie_typed<QT,2,false>(src,args,lds); \
-    case 3: return launch_conv2d_tie_typed<QT,3,false>(src,args,lds); \
-    default: return blend ? launch_conv2d_tie_typed<QT,4,true>(src,args,lds) : launch_conv2d_tie_typed<QT,4,false>(src,args,lds); \
-  }
-  if (is_float)
-    { MH_LAYOUT(float) }
-  MH_LAYOUT(uint16_t)
-#undef MH_LAYOUT
+  return dispatch_layout_blend(src.quantum,src.channels,blend,[&](auto L) {
+    return launch_conv2d_tie_typed<typename decltype(L)::Q,L.C,L.BLEND>(src,args,lds); });
 }
 
 } // namespace mh

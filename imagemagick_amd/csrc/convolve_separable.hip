@@ -19,6 +19,7 @@
 // Edge policy: the reference clamps the window per axis (cache.c:2663-2679), so does each pass.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 #include "tie_check.hpp"
 #include "separable_args.hpp"
 #include <cmath>
@@ -308,23 +309,8 @@ MhStatus launch_separable_exact(const View &src,const View &dst,const MhKernelIn
       *handled=true;
       return MH_OK;
     }
-  MhStatus status=MH_OK;
-#define MH_LAYOUT(QT) \
-  switch (src.channels) \
-  { \
-    case 1: status=separable_typed<QT,1,false>(src,a,horizontal,vertical,work); break; \
-    case 2: status=blend ? separable_typed<QT,2,true>(src,a,horizontal,vertical,work) : \
-      separable_typed<QT,2,false>(src,a,horizontal,vertical,work); break; \
-    case 3: status=separable_typed<QT,3,false>(src,a,horizontal,vertical,work); break; \
-    default: status=blend ? separable_typed<QT,4,true>(src,a,horizontal,vertical,work) : \
-      separable_typed<QT,4,false>(src,a,horizontal,vertical,work); break; \
-  }
-  if (is_float)
-    { MH_LAYOUT(float) }
-  else
-    { MH_LAYOUT(uint16_t) }
-#undef MH_LAYOUT
-  MH_TRY(status);
+  MH_TRY(dispatch_layout_blend(src.quantum,src.channels,blend,[&](auto L) {
+    return separable_typed<typename decltype(L)::Q,L.C,L.BLEND>(src,a,horizontal,vertical,work); }));
   *handled=true;
   return MH_OK;
 }

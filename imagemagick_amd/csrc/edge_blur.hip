@@ -33,6 +33,7 @@
 // is BlurGaussian(255, intensity_sigma).  NaN samples are out of scope for both operators.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -41,7 +42,7 @@ namespace mh {
 
 #include "pixel_intensity.inc.hpp"
 
-constexpr int kEdgeBlock=16;                 // outputs per workgroup: kEdgeBlock x kEdgeBlock
+constexpr int kEdgeBlock=kWindowBlock;       // outputs per workgroup: kEdgeBlock x kEdgeBlock
 constexpr size_t kEdgeMaxLds=131072;         // bytes of the staged tile
 constexpr int kIntensityTable=512;           // 2*(MaxIntensity+1) doubles, 511 of them used
 
@@ -294,8 +295,7 @@ static bool edge_layout(size_t W,size_t H,size_t fixed_bytes,size_t pixel_bytes,
 
 static MhStatus edge_frame(const View &src,const View &dst,const Roles &roles,const char *what,EdgeArgs *a)
 {
-  if ((src.columns > 0x7fffffffu-kEdgeBlock) || ((src.rows+kEdgeBlock-1)/kEdgeBlock > 65535u))
-    return fail(MH_UNSUPPORTED,"%s: %zux%zu frame is outside the launch grid",what,src.columns,src.rows);
+  MH_TRY(window_grid_check(what,src));
   a->src=src.pixels;
   a->dst=dst.pixels;
   a->columns=(int) src.columns;
@@ -308,7 +308,7 @@ static MhStatus edge_frame(const View &src,const View &dst,const Roles &roles,co
 template<typename Q,int C,bool BILATERAL>
 static MhStatus edge_launch(const EdgeArgs &a,size_t lds,hipStream_t stream)
 {
-  const dim3 grid((unsigned) ((a.columns+kEdgeBlock-1)/kEdgeBlock),(unsigned) ((a.rows+kEdgeBlock-1)/kEdgeBlock));
+  const dim3 grid=window_grid(a.columns,a.rows);
   if constexpr (BILATERAL)
     {
       MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bilateral_blur_kernel<Q,C>),
@@ -330,16 +330,8 @@ static MhStatus edge_launch(const EdgeArgs &a,size_t lds,hipStream_t stream)
 template<bool BILATERAL>
 static MhStatus edge_dispatch(const View &src,const EdgeArgs &a,size_t lds)
 {
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: return edge_launch<QT,1,BILATERAL>(a,lds,src.stream); \
-    case 2: return edge_launch<QT,2,BILATERAL>(a,lds,src.stream); \
-    case 3: return edge_launch<QT,3,BILATERAL>(a,lds,src.stream); \
-    default: return edge_launch<QT,4,BILATERAL>(a,lds,src.stream); }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return edge_launch<typename decltype(L)::Q,L.C,BILATERAL>(a,lds,src.stream); });
 }
 
 MhStatus launch_bilateral_blur(const View &src,const View &dst,size_t width,size_t height,

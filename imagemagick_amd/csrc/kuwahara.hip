@@ -29,12 +29,13 @@
 // w <= 43.  NaN and infinite samples are out of scope.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 
 #include <algorithm>
 
 namespace mh {
 
-constexpr int kKuwaharaBlock=16;                 // outputs per workgroup: kKuwaharaBlock x kKuwaharaBlock
+constexpr int kKuwaharaBlock=kWindowBlock;       // outputs per workgroup: kKuwaharaBlock x kKuwaharaBlock
 constexpr size_t kKuwaharaMaxLds=131072;         // bytes of the staged planes and the variance map
 
 struct KuwaharaArgs
@@ -223,8 +224,7 @@ static MhStatus kuwahara_plan(const View &src,double radius,KuwaharaArgs *a,size
   const size_t w=(size_t) radius+1;
   if ((src.channels < 1) || (src.channels > 4))
     return fail(MH_UNSUPPORTED,"KuwaharaImage: %d channels",src.channels);
-  if ((src.columns > 0x7fffffffu-kKuwaharaBlock) || ((src.rows+kKuwaharaBlock-1)/kKuwaharaBlock > 65535u))
-    return fail(MH_UNSUPPORTED,"KuwaharaImage: %zux%zu frame is outside the launch grid",src.columns,src.rows);
+  MH_TRY(window_grid_check("KuwaharaImage",src));
   if (!kuwahara_layout(w,src.channels,src.quantum == MH_QUANTUM_U16 ? 2u : 4u,a,lds) ||
       (*lds > (size_t) lds_bytes_per_workgroup(src.device)))
     return fail(MH_UNSUPPORTED,"KuwaharaImage: a %zux%zu window does not fit the LDS tile",w,w);
@@ -241,12 +241,10 @@ MhStatus kuwahara_check(const View &src,double radius)
 template<typename Q,int C>
 static MhStatus kuwahara_launch(const KuwaharaArgs &a,size_t lds,hipStream_t stream)
 {
-  const dim3 grid((unsigned) ((a.columns+kKuwaharaBlock-1)/kKuwaharaBlock),
-    (unsigned) ((a.rows+kKuwaharaBlock-1)/kKuwaharaBlock));
   MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kuwahara_kernel<Q,C>),
     hipFuncAttributeMaxDynamicSharedMemorySize,(int) kKuwaharaMaxLds));
   ProfileScope prof("kuwahara",stream);
-  hipLaunchKernelGGL((kuwahara_kernel<Q,C>),grid,dim3(kKuwaharaBlock*kKuwaharaBlock),lds,stream,a);
+  hipLaunchKernelGGL((kuwahara_kernel<Q,C>),window_grid(a.columns,a.rows),dim3(kKuwaharaBlock*kKuwaharaBlock),lds,stream,a);
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
@@ -278,16 +276,8 @@ MhStatus launch_kuwahara(const View &blurred,const View &original,const View &ds
     image->alpha_offset : -1;
   a.gray=(image->colorspace == MH_COLORSPACE_GRAY) || (image->colorspace == MH_COLORSPACE_LINEARGRAY) ||
     (blurred.channels < 3);
-#define MH_CASE(QT) \
-  switch (blurred.channels) { \
-    case 1: return kuwahara_launch<QT,1>(a,lds,blurred.stream); \
-    case 2: return kuwahara_launch<QT,2>(a,lds,blurred.stream); \
-    case 3: return kuwahara_launch<QT,3>(a,lds,blurred.stream); \
-    default: return kuwahara_launch<QT,4>(a,lds,blurred.stream); }
-  if (blurred.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(blurred.quantum,blurred.channels,[&](auto L) {
+    return kuwahara_launch<typename decltype(L)::Q,L.C>(a,lds,blurred.stream); });
 }
 
 } // namespace mh

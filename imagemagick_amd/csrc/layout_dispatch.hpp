@@ -1,0 +1,73 @@
+// Host-side helpers of the kernel launchers: the run-time pixel layout (Quantum type, channel
+// count, alpha blending) turned into template arguments, and the launch geometry of the operators
+// that stage a window in LDS for 16 x 16 outputs.
+#pragma once
+
+#include "mh_internal.hpp"
+
+namespace mh {
+
+// What f receives: `typename decltype(L)::Q`, `L.C` and `L.BLEND` are compile-time values.
+template<typename Q_,int C_,bool BLEND_=false>
+struct Layout
+{
+  using Q=Q_;
+  static constexpr int C=C_;
+  static constexpr bool BLEND=BLEND_;
+};
+
+// f(Layout<Q,C>{}) with Q = uint16_t (MH_QUANTUM_U16) or float and C = channels; a channel count
+// other than 1, 2 and 3 goes to C = 4.
+template<class F>
+static inline auto dispatch_layout(MhQuantumKind quantum,int channels,F &&f)
+{
+  const auto typed=[&](auto q)
+  {
+    using Q=decltype(q);
+    switch (channels)
+    {
+      case 1: return f(Layout<Q,1>{});
+      case 2: return f(Layout<Q,2>{});
+      case 3: return f(Layout<Q,3>{});
+      default: return f(Layout<Q,4>{});
+    }
+  };
+  return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
+}
+
+// ... with BLEND = blend where the last channel can be an alpha (C = 2 or 4): <Q,1,true> and
+// <Q,3,true> are never instantiated.
+template<class F>
+static inline auto dispatch_layout_blend(MhQuantumKind quantum,int channels,bool blend,F &&f)
+{
+  return dispatch_layout(quantum,channels,[&](auto L)
+  {
+    using Q=typename decltype(L)::Q;
+    if constexpr ((L.C == 2) || (L.C == 4))
+      {
+        if (blend)
+          return f(Layout<Q,L.C,true>{});
+      }
+    return f(L);
+  });
+}
+
+// ------------------------------------------------------------ 16 x 16 outputs per workgroup
+// StatisticImage, the edge-preserving blurs and KuwaharaImage: a workgroup of kWindowBlock^2 threads
+// stages the window of kWindowBlock x kWindowBlock outputs in LDS.
+constexpr int kWindowBlock=16;
+
+// MH_UNSUPPORTED when the frame does not fit the grid (or the kernels' int coordinates)
+static inline MhStatus window_grid_check(const char *what,const View &src)
+{
+  if ((src.columns > 0x7fffffffu-kWindowBlock) || ((src.rows+kWindowBlock-1)/kWindowBlock > 65535u))
+    return fail(MH_UNSUPPORTED,"%s: %zux%zu frame is outside the launch grid",what,src.columns,src.rows);
+  return MH_OK;
+}
+
+static inline dim3 window_grid(int columns,int rows)
+{
+  return dim3((unsigned) ((columns+kWindowBlock-1)/kWindowBlock),(unsigned) ((rows+kWindowBlock-1)/kWindowBlock));
+}
+
+} // namespace mh

@@ -19,6 +19,7 @@
 // (scalar loads).  Min/max methods compare in the Quantum domain (exact).
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 #include <vector>
 
 #include <cmath>
@@ -1711,22 +1712,10 @@ static MhStatus try_convex(const View &src,const View &dst,bool dilate,const std
   a.changed=changed;
   dim3 grid((unsigned) ((src.columns+kCTW-1)/kCTW),(unsigned) ((src.rows+kCTR-1)/kCTR));
   ProfileScope prof("morph_convex",src.stream);
-  MhStatus st=MH_OK;
-#define MH_CONVEX(QT) \
-  switch (src.channels) \
-  { \
-    case 1: st=launch_convex<QT,1>(dilate,a,grid,lds,src.stream); break; \
-    case 2: st=launch_convex<QT,2>(dilate,a,grid,lds,src.stream); break; \
-    case 3: st=launch_convex<QT,3>(dilate,a,grid,lds,src.stream); break; \
-    case 4: st=launch_convex<QT,4>(dilate,a,grid,lds,src.stream); break; \
-    default: return MH_OK; \
-  }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CONVEX(uint16_t) }
-  else
-    { MH_CONVEX(float) }
-#undef MH_CONVEX
-  MH_TRY(st);
+  if ((src.channels < 1) || (src.channels > 4))
+    return MH_OK;
+  MH_TRY(dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return launch_convex<typename decltype(L)::Q,L.C>(dilate,a,grid,lds,src.stream); }));
   *handled=true;
   return MH_OK;
 }
@@ -2075,17 +2064,8 @@ MhStatus launch_rotational_blur(const View &src,const View &dst,const double *co
     return fail(MH_UNSUPPORTED,"alpha channel must be the last channel");
   dim3 grid((unsigned) ((a.columns+255)/256),(unsigned) a.rows),block(256);
   ProfileScope prof("rotational_blur",src.stream);
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: hipLaunchKernelGGL((rotational_blur_kernel<QT,1>),grid,block,0,src.stream,a); break; \
-    case 2: hipLaunchKernelGGL((rotational_blur_kernel<QT,2>),grid,block,0,src.stream,a); break; \
-    case 3: hipLaunchKernelGGL((rotational_blur_kernel<QT,3>),grid,block,0,src.stream,a); break; \
-    default: hipLaunchKernelGGL((rotational_blur_kernel<QT,4>),grid,block,0,src.stream,a); break; }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  else
-    { MH_CASE(float) }
-#undef MH_CASE
+  dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    hipLaunchKernelGGL((rotational_blur_kernel<typename decltype(L)::Q,L.C>),grid,block,0,src.stream,a); });
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
@@ -2334,16 +2314,8 @@ static MhStatus despeckle_typed(const View &src,const View &dst,const Roles &rol
 
 MhStatus launch_despeckle(const View &src,const View &dst,const Roles &roles)
 {
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: return despeckle_typed<QT,1>(src,dst,roles); \
-    case 2: return despeckle_typed<QT,2>(src,dst,roles); \
-    case 3: return despeckle_typed<QT,3>(src,dst,roles); \
-    default: return despeckle_typed<QT,4>(src,dst,roles); }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return despeckle_typed<typename decltype(L)::Q,L.C>(src,dst,roles); });
 }
 
 // ---------------------------------------------------------------- WaveletDenoiseImage

@@ -16,6 +16,7 @@
 //   UnsharpMaskImage epilogue              MagickCore/effect.c:4343-4372
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 
 #include <map>
 #include <mutex>
@@ -1466,16 +1467,8 @@ MhStatus launch_histogram(const View &src,int intensity_mode,const MhImage *desc
   unsigned long long *hist)
 {
   IntensityParams ip=intensity_params(desc);
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: return histogram_typed<QT,1>(src,intensity_mode,ip,hist); \
-    case 2: return histogram_typed<QT,2>(src,intensity_mode,ip,hist); \
-    case 3: return histogram_typed<QT,3>(src,intensity_mode,ip,hist); \
-    default: return histogram_typed<QT,4>(src,intensity_mode,ip,hist); }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return histogram_typed<typename decltype(L)::Q,L.C>(src,intensity_mode,ip,hist); });
 }
 
 // ---------------------------------------------------------------- LUT build
@@ -1812,17 +1805,10 @@ MhStatus launch_stretch_levels_apply(const View &img,const unsigned long long *h
   {
     ProfileScope prof("apply_lut",img.stream);
     const dim3 apply_grid(stream_grid((n+3)/4)),block(256);
-#define MH_CASE(QT) \
-    switch (img.channels) { \
-      case 1: hipLaunchKernelGGL((stretch_apply_levels_kernel<QT,1>),apply_grid,block,0,img.stream,static_cast<QT *>(img.pixels),n,levels,update_mask,colour_flag); break; \
-      case 2: hipLaunchKernelGGL((stretch_apply_levels_kernel<QT,2>),apply_grid,block,0,img.stream,static_cast<QT *>(img.pixels),n,levels,update_mask,colour_flag); break; \
-      case 3: hipLaunchKernelGGL((stretch_apply_levels_kernel<QT,3>),apply_grid,block,0,img.stream,static_cast<QT *>(img.pixels),n,levels,update_mask,colour_flag); break; \
-      default: hipLaunchKernelGGL((stretch_apply_levels_kernel<QT,4>),apply_grid,block,0,img.stream,static_cast<QT *>(img.pixels),n,levels,update_mask,colour_flag); break; }
-    if (img.quantum == MH_QUANTUM_U16)
-      { MH_CASE(uint16_t) }
-    else
-      { MH_CASE(float) }
-#undef MH_CASE
+    dispatch_layout(img.quantum,img.channels,[&](auto L) {
+      using Q=typename decltype(L)::Q;
+      hipLaunchKernelGGL((stretch_apply_levels_kernel<Q,L.C>),apply_grid,block,0,img.stream,
+        static_cast<Q *>(img.pixels),n,levels,update_mask,colour_flag); });
   }
   MH_HIP(hipGetLastError());
   return MH_OK;
@@ -2043,16 +2029,8 @@ MhStatus launch_apply_lut(const View &img,const void *lut,uint32_t apply_mask,co
       case 3: return apply_lut_shared<3>(img,lut,shared_column,mask,device_mask);
       default: return apply_lut_shared<4>(img,lut,shared_column,mask,device_mask);
     }
-#define MH_CASE(QT) \
-  switch (img.channels) { \
-    case 1: return apply_lut_typed<QT,1>(img,lut,mask,device_mask); \
-    case 2: return apply_lut_typed<QT,2>(img,lut,mask,device_mask); \
-    case 3: return apply_lut_typed<QT,3>(img,lut,mask,device_mask); \
-    default: return apply_lut_typed<QT,4>(img,lut,mask,device_mask); }
-  if (img.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(img.quantum,img.channels,[&](auto L) {
+    return apply_lut_typed<typename decltype(L)::Q,L.C>(img,lut,mask,device_mask); });
 }
 
 
@@ -2207,16 +2185,8 @@ MhStatus launch_composite(const View &canvas,const View &source,int kind,const R
   if ((canvas.columns != source.columns) || (canvas.rows != source.rows) ||
       (canvas.channels != source.channels) || (canvas.quantum != source.quantum))
     return fail(MH_BAD_ARGUMENT,"composite: canvas and source differ in geometry");
-#define MH_CASE(QT) \
-  switch (canvas.channels) { \
-    case 1: return composite_typed<QT,1>(canvas,source,kind,roles); \
-    case 2: return composite_typed<QT,2>(canvas,source,kind,roles); \
-    case 3: return composite_typed<QT,3>(canvas,source,kind,roles); \
-    default: return composite_typed<QT,4>(canvas,source,kind,roles); }
-  if (canvas.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(canvas.quantum,canvas.channels,[&](auto L) {
+    return composite_typed<typename decltype(L)::Q,L.C>(canvas,source,kind,roles); });
 }
 
 // ---------------------------------------------------------------- ContrastImage / ModulateImage
@@ -2858,17 +2828,10 @@ MhStatus launch_grayscale(const View &img,int method,const MhImage *desc)
   const int is_rgb=desc->colorspace == MH_COLORSPACE_RGB;
   const int is_srgb=desc->colorspace == MH_COLORSPACE_SRGB;
   ProfileScope prof("grayscale",img.stream);
-#define MH_CASE(QT) \
-  switch (img.channels) { \
-    case 1: hipLaunchKernelGGL((grayscale_kernel<QT,1>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,method,is_rgb,is_srgb); break; \
-    case 2: hipLaunchKernelGGL((grayscale_kernel<QT,2>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,method,is_rgb,is_srgb); break; \
-    case 3: hipLaunchKernelGGL((grayscale_kernel<QT,3>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,method,is_rgb,is_srgb); break; \
-    default: hipLaunchKernelGGL((grayscale_kernel<QT,4>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,method,is_rgb,is_srgb); break; }
-  if (img.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  else
-    { MH_CASE(float) }
-#undef MH_CASE
+  dispatch_layout(img.quantum,img.channels,[&](auto L) {
+    using Q=typename decltype(L)::Q;
+    hipLaunchKernelGGL((grayscale_kernel<Q,L.C>),dim3(stream_grid(n)),dim3(256),0,img.stream,
+      static_cast<Q *>(img.pixels),n,method,is_rgb,is_srgb); });
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
@@ -2954,17 +2917,10 @@ MhStatus launch_function(const View &img,int function,size_t count,const double 
     fp.p[k]=k < (int) count ? parameters[k] : 0.0;
   const size_t n=img.columns*img.rows;
   ProfileScope prof("function",img.stream);
-#define MH_CASE(QT) \
-  switch (img.channels) { \
-    case 1: hipLaunchKernelGGL((function_kernel<QT,1>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,fp,mask); break; \
-    case 2: hipLaunchKernelGGL((function_kernel<QT,2>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,fp,mask); break; \
-    case 3: hipLaunchKernelGGL((function_kernel<QT,3>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,fp,mask); break; \
-    default: hipLaunchKernelGGL((function_kernel<QT,4>),dim3(stream_grid(n)),dim3(256),0,img.stream,static_cast<QT *>(img.pixels),n,fp,mask); break; }
-  if (img.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  else
-    { MH_CASE(float) }
-#undef MH_CASE
+  dispatch_layout(img.quantum,img.channels,[&](auto L) {
+    using Q=typename decltype(L)::Q;
+    hipLaunchKernelGGL((function_kernel<Q,L.C>),dim3(stream_grid(n)),dim3(256),0,img.stream,
+      static_cast<Q *>(img.pixels),n,fp,mask); });
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
@@ -3096,16 +3052,8 @@ static MhStatus unsharp_typed(const View &src,const View &blur,const View &dst,d
 MhStatus launch_unsharp_epilogue(const View &src,const View &blur,const View &dst,double gain,
   double threshold,const Roles &roles)
 {
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: return unsharp_typed<QT,1>(src,blur,dst,gain,threshold,roles.copy_mask); \
-    case 2: return unsharp_typed<QT,2>(src,blur,dst,gain,threshold,roles.copy_mask); \
-    case 3: return unsharp_typed<QT,3>(src,blur,dst,gain,threshold,roles.copy_mask); \
-    default: return unsharp_typed<QT,4>(src,blur,dst,gain,threshold,roles.copy_mask); }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return unsharp_typed<typename decltype(L)::Q,L.C>(src,blur,dst,gain,threshold,roles.copy_mask); });
 }
 
 // ------------------------------------------- separable 2-D convolution, FAST
@@ -3157,42 +3105,28 @@ void separable_finish_kernel(const float *sums,uint16_t *dst,size_t npixels)
 
 MhStatus launch_premultiply(const View &src,const View &sums,bool blend)
 {
+  if ((src.channels < 1) || (src.channels > 4))
+    return fail(MH_UNSUPPORTED,"separable convolution: %d channels",src.channels);
   const size_t n=src.columns*src.rows;
   const uint16_t *in=static_cast<const uint16_t *>(src.pixels);
   float *out=static_cast<float *>(sums.pixels);
   ProfileScope prof("premultiply",src.stream);
-#define MH_CASE(CV,BV) \
-  hipLaunchKernelGGL((premultiply_kernel<CV,BV>),dim3(stream_grid(n)),dim3(256),0,src.stream,in,out,n)
-  switch (src.channels)
-  {
-    case 1: MH_CASE(1,false); break;
-    case 2: if (blend) MH_CASE(2,true); else MH_CASE(2,false); break;
-    case 3: MH_CASE(3,false); break;
-    case 4: if (blend) MH_CASE(4,true); else MH_CASE(4,false); break;
-    default: return fail(MH_UNSUPPORTED,"separable convolution: %d channels",src.channels);
-  }
-#undef MH_CASE
+  dispatch_layout_blend(src.quantum,src.channels,blend,[&](auto L) {
+    hipLaunchKernelGGL((premultiply_kernel<L.C,L.BLEND>),dim3(stream_grid(n)),dim3(256),0,src.stream,in,out,n); });
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
 
 MhStatus launch_separable_finish(const View &sums,const View &dst,bool blend)
 {
+  if ((dst.channels < 1) || (dst.channels > 4))
+    return fail(MH_UNSUPPORTED,"separable convolution: %d channels",dst.channels);
   const size_t n=dst.columns*dst.rows;
   const float *in=static_cast<const float *>(sums.pixels);
   uint16_t *out=static_cast<uint16_t *>(dst.pixels);
   ProfileScope prof("separable_finish",dst.stream);
-#define MH_CASE(CV,BV) \
-  hipLaunchKernelGGL((separable_finish_kernel<CV,BV>),dim3(stream_grid(n)),dim3(256),0,dst.stream,in,out,n)
-  switch (dst.channels)
-  {
-    case 1: MH_CASE(1,false); break;
-    case 2: if (blend) MH_CASE(2,true); else MH_CASE(2,false); break;
-    case 3: MH_CASE(3,false); break;
-    case 4: if (blend) MH_CASE(4,true); else MH_CASE(4,false); break;
-    default: return fail(MH_UNSUPPORTED,"separable convolution: %d channels",dst.channels);
-  }
-#undef MH_CASE
+  dispatch_layout_blend(dst.quantum,dst.channels,blend,[&](auto L) {
+    hipLaunchKernelGGL((separable_finish_kernel<L.C,L.BLEND>),dim3(stream_grid(n)),dim3(256),0,dst.stream,in,out,n); });
   MH_HIP(hipGetLastError());
   return MH_OK;
 }

@@ -21,6 +21,7 @@
 // words, so Q16 and float Quantum share one selection code path; the other two stage raw Quantum.
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -36,7 +37,7 @@ enum
 
 enum StatRoute { SR_NET16=0,SR_NET32=1,SR_SELECT=2,SR_EXTREME=3,SR_MOMENT=4 };
 
-constexpr int kStatBlock=16;                 // outputs per workgroup: kStatBlock x kStatBlock
+constexpr int kStatBlock=kWindowBlock;       // outputs per workgroup: kStatBlock x kStatBlock
 constexpr size_t kStatMaxLds=65536;          // bytes of one staged channel window
 
 struct StatArgs
@@ -381,9 +382,9 @@ static const char *const kStatRouteNames[]={"statistic_rank_net16","statistic_ra
 template<typename Q,int C,int ROUTE>
 static MhStatus statistic_launch(const StatArgs &a,size_t lds,hipStream_t stream)
 {
-  const dim3 grid((unsigned) ((a.columns+kStatBlock-1)/kStatBlock),(unsigned) ((a.rows+kStatBlock-1)/kStatBlock));
   ProfileScope prof(kStatRouteNames[ROUTE],stream);
-  hipLaunchKernelGGL((statistic_kernel<Q,C,ROUTE>),grid,dim3(kStatBlock*kStatBlock),lds,stream,a);
+  hipLaunchKernelGGL((statistic_kernel<Q,C,ROUTE>),window_grid(a.columns,a.rows),dim3(kStatBlock*kStatBlock),lds,
+    stream,a);
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
@@ -415,9 +416,7 @@ MhStatus launch_statistic(const View &src,const View &dst,int type,size_t width,
   if ((W > 4096) || (H > 4096) ||
       ((W+kStatBlock-1)*(H+kStatBlock-1)*element > kStatMaxLds))
     return fail(MH_UNSUPPORTED,"StatisticImage: a %zux%zu window does not fit the LDS tile",W,H);
-  if ((src.columns > 0x7fffffffu-kStatBlock) || ((src.rows+kStatBlock-1)/kStatBlock > 65535u))
-    return fail(MH_UNSUPPORTED,"StatisticImage: %zux%zu frame is outside the launch grid",
-      src.columns,src.rows);
+  MH_TRY(window_grid_check("StatisticImage",src));
   if ((src.columns == 0) || (src.rows == 0))
     return MH_OK;
   const size_t n=W*H;
@@ -435,16 +434,8 @@ MhStatus launch_statistic(const View &src,const View &dst,int type,size_t width,
   a.type=type;
   a.copy_mask=roles.copy_mask;
   const size_t lds=((size_t) a.tile_w*(size_t) a.tile_h*element+15u) & ~(size_t) 15u;
-#define MH_CASE(QT) \
-  switch (src.channels) { \
-    case 1: return statistic_route<QT,1>(a,route,lds,src.stream); \
-    case 2: return statistic_route<QT,2>(a,route,lds,src.stream); \
-    case 3: return statistic_route<QT,3>(a,route,lds,src.stream); \
-    default: return statistic_route<QT,4>(a,route,lds,src.stream); }
-  if (src.quantum == MH_QUANTUM_U16)
-    { MH_CASE(uint16_t) }
-  MH_CASE(float)
-#undef MH_CASE
+  return dispatch_layout(src.quantum,src.channels,[&](auto L) {
+    return statistic_route<typename decltype(L)::Q,L.C>(a,route,lds,src.stream); });
 }
 
 } // namespace mh

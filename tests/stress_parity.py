@@ -213,6 +213,12 @@ def draw_enhance_case(op):
         else:
             # (small angles often: the sample count grows with the angle and the reference's CPU time with it)
             angle = float(rng.uniform(-360.0, 360.0)) if rng.random() < 0.3 else float(rng.uniform(-20.0, 20.0))
+            # effect.c:3188-3199, :3262-3267: n = |4*radians*sqrt(blur_radius) + 2| samples per pixel.  A small negative angle gives
+            # n = 0 (the reference fails to allocate its tables) or n = 1 (its pixel loop steps by n-1 = 0 and never
+            # ends); the library declines both.  There is nothing to compare there: the mirrored angle instead
+            blur_radius = float(np.hypot((cols - 1) / 2.0, (rows - 1) / 2.0))
+            if int(abs(4.0 * np.pi * angle / 180.0 * np.sqrt(blur_radius) + 2.0)) < 2:
+                angle = -angle
             case.update(name="rotational_blur", args=(angle,))
     else:
         rows, cols = int(rng.integers(33, 601)), int(rng.integers(33, 601))

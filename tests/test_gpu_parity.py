@@ -2842,3 +2842,142 @@ def test_operators_are_reentrant_across_threads_and_streams(im, refmod):
         assert "blur_fused_exact" in launched and launched <= {"blur_fused_exact", "conv_row", "conv_column"}, launched
     finally:
         im.set_precision(im.PRECISION_EXACT)
+
+
+# ------------------------------------------------- every pixel layout of a launcher
+# The launchers turn (Quantum type, channel count[, alpha blending]) into template arguments (layout_dispatch.hpp).  A
+# wrong pairing at one launcher garbles every pixel of a frame of any size, so the layouts the tests above leave out
+# are run here on the smallest frames that still cross a block edge where the kernel has one.
+LAYOUTS = [(dtype, channels) for dtype in (Q16, HDRI) for channels in (1, 2, 3, 4)]
+BLEND_LAYOUTS = [(dtype, channels, alpha) for dtype in (Q16, HDRI)
+                 for channels, alpha in ((1, False), (2, True), (2, False), (3, False), (4, True), (4, False))]
+
+
+@pytest.mark.parametrize("dtype,channels", LAYOUTS)
+def test_function_every_layout(im, refmod, dtype, channels):
+    px = make_pixels(5, 7, channels, dtype, seed=channels)
+    dev, ref = run_pair(im, refmod, px)
+    params = (0.3, -1.2, 1.5, 0.1)
+    assert_parity(im.function_image(dev, "Polynomial", params).numpy(), ref.function("Polynomial", params).numpy(), True,
+                  "function c%d" % channels)
+
+
+@pytest.mark.parametrize("dtype,channels", LAYOUTS)
+def test_grayscale_every_layout(im, refmod, dtype, channels):
+    """One and two channels: a gray[+alpha] frame, whose red, green and blue are the gray sample."""
+    px = make_pixels(5, 7, channels, dtype, seed=channels)
+    dev, ref = run_pair(im, refmod, px, colorspace="sRGB" if channels >= 3 else "Gray")
+    got = im.grayscale_image(dev, "Rec709Luma").numpy()
+    want = ref.grayscale("Rec709Luma").numpy()
+    assert_parity(np.ascontiguousarray(got[:, :, 0]), np.ascontiguousarray(want[:, :, 0]), True, "grayscale c%d" % channels)
+    if channels in (2, 4):
+        assert np.array_equal(got[:, :, -1], want[:, :, -1])
+
+
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+def test_contrast_stretch_gray_alpha(im, refmod, dtype):
+    """The layout test_contrast_stretch leaves out."""
+    px = make_pixels(5, 7, 2, dtype)
+    dev, ref = run_pair(im, refmod, px)
+    assert_parity(im.contrast_stretch_image(dev, 1.0, 33.0).numpy(), ref.contrast_stretch(1.0, 33.0).numpy(), True,
+                  "contrast-stretch c2")
+
+
+@pytest.mark.parametrize("dtype", [Q16, HDRI])
+def test_compound_morphology_with_difference_gray_alpha(im, refmod, dtype):
+    """The layout test_compound_morphology_with_difference leaves out (CompositeImage(Difference) on the device)."""
+    px = make_pixels(5, 7, 2, dtype)
+    dev, ref = run_pair(im, refmod, px)
+    assert_parity(im.morphology_image(dev, "EdgeIn", 1, "Disk:2.5").numpy(), ref.morphology("EdgeIn", 1, "Disk:2.5").numpy(),
+                  True, "EdgeIn Disk:2.5 c2")
+
+
+@pytest.mark.parametrize("dtype,channels", LAYOUTS)
+def test_unsharp_mask_epilogue_kernel_every_layout(im, refmod, dtype, channels, options):
+    """A kernel too short for the column pass that applies the epilogue as it stores, the one-launch Q16 form switched
+    off: blur, then unsharp_kernel."""
+    import bench
+    options.set("MAGICKHIP_NO_FUSED_UNSHARP", "1")
+    px = make_pixels(5, 7, channels, dtype, seed=channels)
+    dev, ref = run_pair(im, refmod, px)
+    holder = {}
+    launched = set(bench.kernel_profile(im, lambda: holder.update(out=im.unsharp_mask_image(dev, 0.0, 1.0, 1.5, 0.02)), 1))
+    assert "unsharp_epilogue" in launched, launched
+    assert_parity(holder["out"].numpy(), ref.unsharp(0.0, 1.0, 1.5, 0.02).numpy(), True, "unsharp epilogue c%d" % channels)
+
+
+@pytest.mark.parametrize("dtype,channels", LAYOUTS)
+@pytest.mark.parametrize("method", ["Dilate", "Erode"])
+def test_convex_kernel_every_layout(im, refmod, method, dtype, channels, options):
+    """morph_convex_kernel (the union-of-rectangles kernel switched off), a frame of more than one tile."""
+    import bench
+    options.set("MAGICKHIP_NO_RECTS", "1")
+    px = make_pixels(17, 33, channels, dtype, seed=channels)
+    dev, ref = run_pair(im, refmod, px)
+    holder = {}
+    launched = set(bench.kernel_profile(im, lambda: holder.update(out=im.morphology_image(dev, method, 1, "Disk:3")), 1))
+    assert "morph_convex" in launched, launched
+    assert_parity(holder["out"].numpy(), ref.morphology(method, 1, "Disk:3").numpy(), True, "%s Disk:3 c%d" % (method, channels))
+
+
+def plain_channels_reference(refmod, px, kernel):
+    """Convolve on a frame without alpha weighting: every channel on its own."""
+    planes = [refmod.RefImage(px[:, :, c].copy()).set_artifact("convolve:scale", "!").morphology("Convolve", 1, kernel).numpy()
+              for c in range(px.shape[2])]
+    return np.concatenate([p.reshape(px.shape[0], px.shape[1], 1) for p in planes], axis=2)
+
+
+def convolve_every_layout(im, refmod, kernel, dtype, channels, alpha, precision, expected):
+    """Convolve with a normalised kernel on a 17 x 33 frame against the reference; `expected` kernels must be launched."""
+    import bench
+    px = make_pixels(17, 33, channels, dtype, seed=channels + len(kernel))
+    if alpha:
+        px[3:9, 5:20, channels - 1] = px[3:9, 5:20, channels - 1] % 4
+        px[12:15, 20:30, channels - 1] = 0
+    dev = im.Image(to_device(px), has_alpha=alpha)
+    if alpha or channels in (1, 3):
+        want = refmod.RefImage(px).set_artifact("convolve:scale", "!").morphology("Convolve", 1, kernel).numpy().reshape(px.shape)
+    else:
+        want = plain_channels_reference(refmod, px, kernel)
+    holder = {}
+    im.set_precision(precision)
+    try:
+        launched = set(bench.kernel_profile(
+            im, lambda: holder.update(out=im.morphology_image(dev, "Convolve", 1, kernel, scale=(1.0, 1))), 1))
+    finally:
+        im.set_precision(im.PRECISION_EXACT)
+    assert expected <= launched, launched
+    return holder["out"].numpy().reshape(px.shape), want
+
+
+@pytest.mark.parametrize("dtype,channels,alpha", BLEND_LAYOUTS)
+@pytest.mark.parametrize("folded", [True, False])
+def test_separable_2d_convolve_exact_every_layout(im, refmod, dtype, channels, alpha, folded, options):
+    """convolve.hip's folded passes and convolve_separable.hip's four launches; with test_separable_2d_convolve_exact's
+    layouts, gray + alpha without alpha weighting."""
+    options.set("MAGICKHIP_NO_EXACT_2D", "1")
+    if not folded:
+        options.set("MAGICKHIP_NO_SEPARABLE_FOLD", "1")
+    expected = {"separable_row_sums", "separable_column_finish", "separable_settle"} if folded else {"separable_finish"}
+    got, want = convolve_every_layout(im, refmod, "Gaussian:0x2", dtype, channels, alpha, im.PRECISION_EXACT, expected)
+    assert_parity(got, want, True, "separable Gaussian:0x2 c%d alpha=%s folded=%s" % (channels, alpha, folded))
+
+
+@pytest.mark.parametrize("dtype,channels,alpha", BLEND_LAYOUTS)
+def test_convolve_2d_fused_fp64_every_layout(im, refmod, dtype, channels, alpha, options):
+    """convolve2d_tie.hip; with test_convolve_2d_fused_fp64_with_tie_check's layouts, gray + alpha without alpha
+    weighting."""
+    options.set("MAGICKHIP_NO_EXACT_2D", "1")
+    got, want = convolve_every_layout(im, refmod, "Disk:7.3", dtype, channels, alpha, im.PRECISION_EXACT, {"conv2d_tie"})
+    assert_parity(got, want, True, "fused 2-D convolve Disk:7.3 c%d alpha=%s" % (channels, alpha))
+
+
+@pytest.mark.parametrize("channels,alpha", [(1, False), (2, True), (2, False), (3, False), (4, True), (4, False)])
+def test_convolve_fast_premultiplied_passes_every_layout(im, refmod, channels, alpha, options):
+    """premultiply_kernel and separable_finish_kernel (FAST, Q16; the matrix-core passes switched off so that three
+    and four channels take them too): within one level."""
+    options.set("MAGICKHIP_NO_MFMA", "1")
+    options.set("MAGICKHIP_SEPARABLE_SMALL", "1")
+    got, want = convolve_every_layout(im, refmod, "Gaussian:0x2", Q16, channels, alpha, im.PRECISION_FAST,
+                                      {"premultiply", "separable_finish"})
+    assert_parity(got, want, False, "fast separated Gaussian:0x2 c%d alpha=%s" % (channels, alpha))
