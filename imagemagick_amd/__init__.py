@@ -19,7 +19,7 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
                    ALL_CHANNELS, SYNC_CHANNELS)
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
-           "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image",
+           "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image", "clahe_image",
            "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "kuwahara_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
@@ -495,6 +495,15 @@ def equalize_image(image):
     return image
 
 
+def clahe_image(image, width, height, number_bins, clip_limit):
+    """CLAHEImage(image, width, height, number_bins, clip_limit), in place — MagickCore/enhance.c:616.
+    The conversions to and from Lab always run as the bit-identical ones."""
+    lib = _lib.load()
+    _lib.check(lib.MagickHipCLAHEImage(ctypes.byref(image.descriptor()), int(width), int(height), int(number_bins),
+                                       float(clip_limit)))
+    return image
+
+
 def transform_colorspace_contrast_stretch_image(image, colorspace, black_point, white_point):
     """TransformImageColorspace then ContrastStretchImage as one call (the two calls' results; a
     FAST sRGB -> Lab of an RGBA Q16 frame shares its pass over the pixels with the histogram)."""
@@ -662,7 +671,8 @@ def _operators(chain):
     "Dilate", 1, "Disk:15"), ("unsharpmask", 0, 10, 1.0, 0.02), ("resize", columns, rows, "Lanczos"),
     ("equalize",), ("statistic", "Median", width, height), ("bilateralblur", width, height,
     intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold), ("kuwahara",
-    radius, sigma)] -> an MhOperator array (and the byte strings it points at)."""
+    radius, sigma), ("clahe", width, height, number_bins, clip_limit)] -> an MhOperator array (and
+    the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):

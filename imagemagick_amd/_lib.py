@@ -121,7 +121,7 @@ class MhBatchReport(ctypes.Structure):
 
 OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morphology": 5,
              "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9,
-             "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12}
+             "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12, "clahe": 13}
 
 # StatisticOptions, MagickCore/option.c:2183 (lower-case keys) -> MhStatisticType
 STATISTICS = {"undefined": 0, "contrast": 10, "gradient": 1, "maximum": 2, "mean": 3, "median": 4,
@@ -231,6 +231,8 @@ PROTOTYPES = [
     ("MagickHipContrastStretchImage", ctypes.c_int, [_P(MhImage), ctypes.c_double,
                                                      ctypes.c_double, _P(ctypes.c_int)]),
     ("MagickHipEqualizeImage", ctypes.c_int, [_P(MhImage)]),
+    ("MagickHipCLAHEImage", ctypes.c_int, [_P(MhImage), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                           ctypes.c_double]),
     ("MagickHipTransformImageColorspace", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipGrayscaleImage", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipImportImagePixels", ctypes.c_int, [_P(MhImage), ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_size_t,

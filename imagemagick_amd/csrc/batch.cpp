@@ -187,6 +187,12 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
           }
         case MH_OP_RESIZE: case MH_OP_COLORSPACE:
           break;
+        case MH_OP_CLAHE:
+          // width, height, number_bins are size_t arguments of the call
+          for (int k=0; k < 3; k++)
+            if (!(p.op.args[k] >= 0.0) || (p.op.args[k] > 4294967295.0))
+              return fail(MH_BAD_ARGUMENT,"operator %zu: clahe argument %d is %g",i,k,p.op.args[k]);
+          break;
         case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
           p.histogram=true;
           break;
@@ -225,6 +231,8 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       return MagickHipContrastStretchImage(&cur.image,op.args[0],op.args[1],nullptr);
     case MH_OP_EQUALIZE:
       return MagickHipEqualizeImage(&cur.image);
+    case MH_OP_CLAHE:
+      return MagickHipCLAHEImage(&cur.image,(size_t) op.args[0],(size_t) op.args[1],(size_t) op.args[2],op.args[3]);
     default:
       break;
   }
@@ -849,6 +857,8 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
     {
       if (p.op.kind == MH_OP_RESIZE)
         return fail(MH_UNSUPPORTED,"ShardedImage: resize changes the geometry");
+      if (p.op.kind == MH_OP_CLAHE)
+        return fail(MH_UNSUPPORTED,"ShardedImage: CLAHEImage's tile grid belongs to the whole frame");
       if (p.reach == (size_t) -1)
         return fail(MH_UNSUPPORTED,"ShardedImage: iterate-until-convergence has no halo bound");
       reach=p.reach > reach ? p.reach : reach;

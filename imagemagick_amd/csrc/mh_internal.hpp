@@ -437,6 +437,10 @@ void selective_blur_kernel_values(size_t width,double sigma,double *kernel);
 MhStatus kuwahara_check(const View &src,double radius);
 MhStatus launch_kuwahara(const View &blurred,const View &original,const View &dst,double radius,
   const MhImage *image,const MhImage *kuwahara_image);
+// CLAHEImage between its colourspace transforms, in place on channel 0 of a three-colour frame
+// (clahe.hip).  clahe_check: what launch_clahe would decline, asked before the frame is converted
+MhStatus clahe_check(const View &img,size_t width,size_t height,size_t number_bins,double clip_limit);
+MhStatus launch_clahe(const View &img,size_t width,size_t height,size_t number_bins,double clip_limit);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

@@ -445,6 +445,38 @@ MH_API MhStatus MagickHipEqualizeImage(MhImage *image)
   return io.img.commit();
 }
 
+// CLAHEImage, enhance.c:616-785
+MH_API MhStatus MagickHipCLAHEImage(MhImage *image,size_t width,size_t height,size_t number_bins,
+  double clip_limit)
+{
+  MH_TRY(check_image(image,"CLAHEImage"));
+  const MhColorspace from=(MhColorspace) image->colorspace;
+  // the reference re-lays gray frames out as three channels on the way to Lab; four plain channels
+  // are no R,G,B[,A]
+  const uint32_t colour=image->number_channels-(image->alpha_offset >= 0 ? 1u : 0u);
+  if (colour != 3)
+    return fail(MH_UNSUPPORTED,"CLAHEImage needs three colour channels");
+  if ((from != MH_COLORSPACE_LAB) && !colorspace_is_accelerated(from))
+    return fail(MH_UNSUPPORTED,"CLAHEImage: colourspace %d -> Lab is not accelerated",(int) from);
+  InPlace io;
+  MH_TRY(io.open(image));
+  const View &view=io.img.view;
+  MH_TRY(clahe_check(view,width,height,number_bins,clip_limit));
+  // Both conversions run as the bit-identical ones whatever the call's mode: one level of L across
+  // a bin boundary moves a count and with it the mapped value by a whole bin step.  The channel
+  // mask plays no part: the reference's transforms store R, G and B past it (colorspace.c), as
+  // launch_colorspace does, and so does the write-back of L (enhance.c:761).
+  MhImage exact=*image;
+  exact.precision=MH_IMAGE_PRECISION(MH_PRECISION_EXACT);
+  set_call_precision(&exact);
+  if (from != MH_COLORSPACE_LAB)
+    MH_TRY(launch_colorspace(view,from,MH_COLORSPACE_LAB,&exact));
+  MH_TRY(launch_clahe(view,width,height,number_bins,clip_limit));
+  if (from != MH_COLORSPACE_LAB)
+    MH_TRY(launch_colorspace(view,MH_COLORSPACE_LAB,from,&exact));
+  return io.img.commit();
+}
+
 // TransformImageColorspace, colorspace.c:1751-1783
 MH_API MhStatus MagickHipTransformImageColorspace(MhImage *image,MhColorspace colorspace)
 {

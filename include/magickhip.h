@@ -605,6 +605,29 @@ MH_API MhStatus MagickHipContrastStretchImage(MhImage *image,double black_point,
 /* AccelerateEqualizeImage: EqualizeImage, enhance.c:2040-2280. */
 MH_API MhStatus MagickHipEqualizeImage(MhImage *image);
 
+/* CLAHEImage(image,width,height,number_bins,clip_limit), enhance.c:295-785 (no accelerate hook in
+   the reference), in place: TransformImageColorspace to Lab, contrast-limited adaptive histogram
+   equalisation of L over width x height tiles (0: columns>>3 / rows>>3; the frame padded to whole
+   tiles by edge replication; number_bins 0: 128, at most 256), TransformImageColorspace back;
+   image->colorspace ends at its value on entry.  An image already in Lab runs the core alone.
+   Host or device memory, Q16 and float Quantum, R,G,B[,A] layouts in every colourspace
+   MagickHipTransformImageColorspace converts to and from Lab.  Both conversions always run as the
+   bit-identical ones, whatever MhImage::precision or MhSetPrecision say: one level of L across a
+   bin boundary moves a histogram count and the mapped value by a whole bin step.  The channel mask
+   and the traits play no part, as in the reference.
+   Q16: bit-identical to the reference.  Float Quantum: the core is bit-identical on any frame
+   (so a Lab image is); from another colourspace the call equals, bit for bit, this library's own
+   MagickHipTransformImageColorspace(Lab) -> the core -> MagickHipTransformImageColorspace(back),
+   and those float conversions are within 1 ULP of the reference's libm (the library's contract for
+   them), so the whole is not promised bit-identical to the CPU there.
+   MH_UNSUPPORTED (image untouched; the CPU path runs): one- and two-channel frames and four plain
+   channels, a colourspace that is not accelerated, tile maps (tiles x bins x 2 bytes) larger than
+   the frame, a padded frame of 2^32 pixels or more, a negative or NaN clip_limit.
+   MH_BAD_ARGUMENT (the reference divides by zero): a resolved tile width or height of 0
+   (columns < 8 with width 0), number_bins 1. */
+MH_API MhStatus MagickHipCLAHEImage(MhImage *image,size_t width,size_t height,size_t number_bins,
+  double clip_limit);
+
 /* TransformImageColorspace, colorspace.c:1751 — sRGB <-> linear RGB / Lab / XYZ.
    On success image->colorspace is updated. */
 MH_API MhStatus MagickHipTransformImageColorspace(MhImage *image,MhColorspace colorspace);
@@ -747,7 +770,10 @@ typedef enum
   MH_OP_STATISTIC = 9,         /* args: MhStatisticType, width, height */
   MH_OP_BILATERAL_BLUR = 10,   /* args: width, height, intensity_sigma, spatial_sigma */
   MH_OP_SELECTIVE_BLUR = 11,   /* args: radius, sigma, threshold */
-  MH_OP_KUWAHARA = 12          /* args: radius, sigma */
+  MH_OP_KUWAHARA = 12,         /* args: radius, sigma */
+  MH_OP_CLAHE = 13             /* args: width, height, number_bins, clip_limit; MagickHipBatchImages
+                                  only: MagickHipShardedImage returns MH_UNSUPPORTED for it, the
+                                  tile grid belongs to the whole frame, not to a row band */
 } MhOperatorKind;
 
 typedef struct MhOperator

@@ -42,6 +42,7 @@
 #include "MagickCore/colorspace-private.h"
 #include "MagickCore/composite.h"
 #include "MagickCore/morphology.h"
+#include "MagickCore/profile.h"
 
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 
@@ -926,6 +927,15 @@ static MagickBooleanType SetResidentImageColorspace(HipLibrary *library,Image *i
   return(status);
 }
 
+/*
+  Set by AccelerateCLAHEImage when it declines an image outside Lab: CLAHEImage's CPU code then
+  calls TransformImageColorspace twice on this thread (enhance.c:685, :782), and those two calls
+  stay on the CPU too.  One level of L (the default mode's conversion is within one) across a bin
+  boundary moves the equalised value by a whole bin step.
+*/
+static __thread int
+  clahe_transforms_on_cpu = 0;
+
 MagickPrivate MagickBooleanType AccelerateTransformImageColorspace(Image *image,
   const ColorspaceType colorspace,ExceptionInfo *exception)
 {
@@ -935,6 +945,11 @@ MagickPrivate MagickBooleanType AccelerateTransformImageColorspace(Image *image,
   MhStatus
     status;
 
+  if (clahe_transforms_on_cpu > 0)
+    {
+      clahe_transforms_on_cpu--;
+      return(HipDeclined(image,MagickFalse));
+    }
   if (((colorspace == GRAYColorspace) || (colorspace == LinearGRAYColorspace)) &&
       (image->colorspace == sRGBColorspace) && (image->number_channels >= 3) &&
       (IsLayoutAcceleratable(image) != MagickFalse))
@@ -980,6 +995,63 @@ MagickPrivate MagickBooleanType AccelerateTransformImageColorspace(Image *image,
     return(HipDeclined(image,MagickFalse));
   MarkDeviceCopyNewer(image);
   HipAccepted(image);
+  return(SetResidentImageColorspace(call.library,image,colorspace,exception));
+}
+
+/*
+  CLAHEImage's call site (the shim's own hook, shim/patch_hooks.py): the top of the function,
+  enhance.c:660.  The library converts to Lab, equalises L and converts back in one call, both
+  conversions as the bit-identical ones; what AccelerateTransformImageColorspace declines for the
+  two transforms is declined here.  The reference reads its padding through the virtual pixels:
+  Undefined / Edge only (IsLayoutAcceleratable).  A declined call has touched nothing.
+*/
+MagickPrivate MagickBooleanType AccelerateCLAHEImage(Image *image,const size_t width,
+  const size_t height,const size_t number_bins,const double clip_limit,ExceptionInfo *exception)
+{
+  const ColorspaceType
+    colorspace = image->colorspace;
+
+  HipCall
+    call;
+
+  MhStatus
+    status;
+
+  /* a declined call keeps its two transforms on the CPU as well (clahe_transforms_on_cpu) */
+  clahe_transforms_on_cpu=colorspace != LabColorspace ? 2 : 0;
+  if ((image->number_channels < 3) || (IsLayoutAcceleratable(image) == MagickFalse))
+    return(HipDeclined(image,MagickFalse));
+  if (colorspace != LabColorspace)
+    {
+      if ((IsColorspaceAccelerated(colorspace) == MagickFalse) ||
+          (GetImageArtifact(image,"color:illuminant") != (const char *) NULL) ||
+          (GetImageProperty(image,"white-luminance",exception) != (const char *) NULL))
+        return(HipDeclined(image,MagickFalse));
+      if ((colorspace == LogColorspace) &&
+          ((GetImageProperty(image,"gamma",exception) != (const char *) NULL) ||
+           (GetImageProperty(image,"film-gamma",exception) != (const char *) NULL) ||
+           (GetImageProperty(image,"reference-black",exception) != (const char *) NULL) ||
+           (GetImageProperty(image,"reference-white",exception) != (const char *) NULL)))
+        return(HipDeclined(image,MagickFalse));
+    }
+  if (BeginHipCall(&call,image,0,0,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  status=call.library->CLAHEImage(&call.source,width,height,number_bins,clip_limit);
+  (void) EndHipCall(&call,status);
+  if (status != MH_OK)
+    return(HipDeclined(image,MagickFalse));      /* MH_UNSUPPORTED, MH_BAD_ARGUMENT: the CPU path */
+  clahe_transforms_on_cpu=0;
+  MarkDeviceCopyNewer(image);
+  HipAccepted(image);
+  if (colorspace == LabColorspace)
+    return(MagickTrue);
+  /* TransformImageColorspace, colorspace.c:1763-1764 */
+  (void) DeleteImageProfile(image,"icc");
+  (void) DeleteImageProfile(image,"icm");
+  /* what the two SetImageColorspace calls of the transforms leave in the image (gamma, rendering
+     intent, chromaticity, type) */
+  if (SetResidentImageColorspace(call.library,image,LabColorspace,exception) == MagickFalse)
+    return(MagickFalse);
   return(SetResidentImageColorspace(call.library,image,colorspace,exception));
 }
 

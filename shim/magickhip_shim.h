@@ -49,6 +49,7 @@ typedef struct _HipLibrary
   MhStatus (*BilateralBlurImage)(const MhImage *,MhImage *,size_t,size_t,double,double);
   MhStatus (*SelectiveBlurImage)(const MhImage *,MhImage *,double,double,double);
   MhStatus (*KuwaharaImage)(const MhImage *,MhImage *,double,double);
+  MhStatus (*CLAHEImage)(MhImage *,size_t,size_t,size_t,double);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

@@ -178,6 +178,7 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(BilateralBlurImage,"MagickHipBilateralBlurImage");
   MH_RESOLVE(SelectiveBlurImage,"MagickHipSelectiveBlurImage");
   MH_RESOLVE(KuwaharaImage,"MagickHipKuwaharaImage");
+  MH_RESOLVE(CLAHEImage,"MagickHipCLAHEImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

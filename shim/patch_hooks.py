@@ -3,7 +3,7 @@
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
-StatisticImage, BilateralBlurImage, SelectiveBlurImage and KuwaharaImage lack altogether.  Each hook is the reference's own three-line idiom
+StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage and CLAHEImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -47,6 +47,13 @@ extern MagickPrivate Image *AccelerateSelectiveBlurImage(const Image *,const dou
   const double,ExceptionInfo *);
 extern MagickPrivate Image *AccelerateKuwaharaImage(const Image *,const double,const double,
   ExceptionInfo *);
+#endif
+'''
+
+ENHANCE_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate MagickBooleanType AccelerateCLAHEImage(Image *,const size_t,const size_t,
+  const size_t,const double,ExceptionInfo *);
 #endif
 '''
 
@@ -132,7 +139,16 @@ def enhance(text):
     begin = text.index("MagickExport MagickBooleanType ContrastStretchImage(")
     end = text.index("MagickExport", begin + 10)
     body = once(text[begin:end], anchor, hook, "enhance.c")
-    return text[:begin] + body + text[end:]
+    text = text[:begin] + body + text[end:]
+    # CLAHEImage has no accelerate hook in the reference: one at its top, in front of the tile
+    # geometry, so that both colourspace transforms and the equalisation run on the device
+    text = after_includes(text, ENHANCE_PROTOTYPE)
+    anchor = "  range_info.min=0;\n"
+    return in_function(text, "MagickExport MagickBooleanType CLAHEImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  if (AccelerateCLAHEImage(image,width,height,number_bins,clip_limit,exception) != MagickFalse)
+    return(MagickTrue);
+#endif
+''' + anchor, "enhance.c")
 
 
 def colorspace(text):

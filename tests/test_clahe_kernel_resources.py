@@ -1,0 +1,23 @@
+"""The three CLAHEImage kernels (clahe.hip) are in the built library and keep everything in registers
+and LDS: no scratch.  Read from the code objects' metadata (tools/kernel_resources.py); no GPU
+needed."""
+import os
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def test_clahe_kernels_exist_and_do_not_spill():
+    import kernel_resources
+    if not os.path.exists(kernel_resources.DEFAULT_LIBRARY) or not os.path.exists(kernel_resources.OBJCOPY):
+        pytest.skip("library or llvm-objcopy not present")
+    kernels = kernel_resources.kernel_resources()
+    # two Quantum types x R,G,B[,A] for the passes over the frame; the map kernel sees counts only
+    for name, count in (("clahe_histogram_kernel<", 4), ("clahe_interpolate_kernel<", 4), ("clahe_map_kernel(", 1)):
+        rows = [k for k in kernels if name in k["name"]]
+        assert len(rows) == count, (name, [k["name"] for k in rows])
+        for k in rows:
+            assert k["scratch"] == 0, k
