@@ -20,6 +20,8 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
            "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image", "clahe_image",
+           "bilevel_image", "auto_threshold_image", "adaptive_threshold_image", "black_threshold_image",
+           "white_threshold_image", "range_threshold_image", "auto_threshold_from_histogram",
            "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "kuwahara_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
@@ -504,6 +506,93 @@ def clahe_image(image, width, height, number_bins, clip_limit):
     return image
 
 
+def _auto_threshold_method(method):
+    if isinstance(method, str):
+        key = method.lower()
+        if key not in _lib.AUTO_THRESHOLD:
+            raise ValueError("unknown auto-threshold method %r" % method)
+        return _lib.AUTO_THRESHOLD[key]
+    return int(method)
+
+
+def bilevel_image(image, threshold):
+    """BilevelImage(image, threshold), in place — MagickCore/threshold.c:805; threshold in Quantum
+    units.  A frame outside the gray colourspaces ends up tagged sRGB, as in the reference."""
+    lib = _lib.load()
+    d = image.descriptor()
+    _lib.check(lib.MagickHipBilevelImage(ctypes.byref(d), float(threshold)))
+    names = {v: k for k, v in COLORSPACES.items()}
+    image.colorspace = names.get(int(d.colorspace), image.colorspace)
+    return image
+
+
+def auto_threshold_image(image, method="otsu"):
+    """AutoThresholdImage(image, method), in place — MagickCore/threshold.c:660.  method: "Kapur",
+    "OTSU", "Triangle" or an MhAutoThresholdMethod value.  Returns (image, percentage): the value
+    the reference stores as the auto-threshold:threshold property."""
+    lib = _lib.load()
+    d = image.descriptor()
+    percent = ctypes.c_double(0.0)
+    _lib.check(lib.MagickHipAutoThresholdImage(ctypes.byref(d), _auto_threshold_method(method), ctypes.byref(percent)))
+    names = {v: k for k, v in COLORSPACES.items()}
+    image.colorspace = names.get(int(d.colorspace), image.colorspace)
+    return image, percent.value
+
+
+def auto_threshold_from_histogram(counts, method="otsu"):
+    """The host half of AutoThresholdImage (threshold.c:392-658, :718-748): the percentage chosen
+    from 256 bin counts.  No device is touched."""
+    lib = _lib.load()
+    counts = np.ascontiguousarray(counts, dtype=np.float64)
+    if counts.shape != (256,):
+        raise ValueError("256 bin counts expected")
+    percent = ctypes.c_double(0.0)
+    _lib.check(lib.MhAutoThresholdFromHistogram(counts.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                _auto_threshold_method(method), ctypes.byref(percent)))
+    return percent.value
+
+
+def adaptive_threshold_image(image, width, height, bias=0.0):
+    """AdaptiveThresholdImage(image, width, height, bias) — MagickCore/threshold.c:182; bias in
+    Quantum units."""
+    return _pair_operator("MagickHipAdaptiveThresholdImage", image, int(width), int(height), float(bias))
+
+
+def _channel_thresholds(image, thresholds):
+    values = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+    if values.size == 1:
+        values = np.repeat(values, image.channels)
+    if values.size != image.channels:
+        raise ValueError("one threshold, or one per stored channel")
+    out = (ctypes.c_double * _lib.MH_MAX_CHANNELS)()
+    for c in range(image.channels):
+        out[c] = float(values[c])
+    return out
+
+
+def black_threshold_image(image, thresholds):
+    """BlackThresholdImage, in place — MagickCore/threshold.c:927.  thresholds: one value or one
+    per stored channel, in Quantum units (the geometry string stays with the caller)."""
+    lib = _lib.load()
+    _lib.check(lib.MagickHipBlackThresholdImage(ctypes.byref(image.descriptor()), _channel_thresholds(image, thresholds)))
+    return image
+
+
+def white_threshold_image(image, thresholds):
+    """WhiteThresholdImage, in place — MagickCore/threshold.c:2518; thresholds as for black_threshold_image."""
+    lib = _lib.load()
+    _lib.check(lib.MagickHipWhiteThresholdImage(ctypes.byref(image.descriptor()), _channel_thresholds(image, thresholds)))
+    return image
+
+
+def range_threshold_image(image, low_black, low_white, high_white, high_black):
+    """RangeThresholdImage, in place — MagickCore/threshold.c:2377; Quantum units."""
+    lib = _lib.load()
+    _lib.check(lib.MagickHipRangeThresholdImage(ctypes.byref(image.descriptor()), float(low_black), float(low_white),
+                                                float(high_white), float(high_black)))
+    return image
+
+
 def transform_colorspace_contrast_stretch_image(image, colorspace, black_point, white_point):
     """TransformImageColorspace then ContrastStretchImage as one call (the two calls' results; a
     FAST sRGB -> Lab of an RGBA Q16 frame shares its pass over the pixels with the histogram)."""
@@ -671,7 +760,8 @@ def _operators(chain):
     "Dilate", 1, "Disk:15"), ("unsharpmask", 0, 10, 1.0, 0.02), ("resize", columns, rows, "Lanczos"),
     ("equalize",), ("statistic", "Median", width, height), ("bilateralblur", width, height,
     intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold), ("kuwahara",
-    radius, sigma), ("clahe", width, height, number_bins, clip_limit)] -> an MhOperator array (and
+    radius, sigma), ("clahe", width, height, number_bins, clip_limit), ("threshold", threshold),
+    ("autothreshold", "OTSU"), ("adaptivethreshold", width, height, bias)] -> an MhOperator array (and
     the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
@@ -690,6 +780,8 @@ def _operators(chain):
             args = [args[0], args[1], FILTERS[args[2].lower()] if len(args) > 2 else FILTERS["lanczos"]]
         elif name == "statistic":
             args = [_lib.STATISTICS[args[0].lower()] if isinstance(args[0], str) else args[0], args[1], args[2]]
+        elif name == "autothreshold":
+            args = [_auto_threshold_method(args[0])]
         for k, a in enumerate(args):
             ops[i].args[k] = float(a)
     return ops, keep

@@ -121,7 +121,11 @@ class MhBatchReport(ctypes.Structure):
 
 OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morphology": 5,
              "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9,
-             "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12, "clahe": 13}
+             "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12, "clahe": 13,
+             "threshold": 14, "autothreshold": 15, "adaptivethreshold": 16}
+
+# AutoThresholdMethod, MagickCore/threshold.h:25-31 (lower-case keys) -> MhAutoThresholdMethod
+AUTO_THRESHOLD = {"undefined": 0, "kapur": 1, "otsu": 2, "triangle": 3}
 
 # StatisticOptions, MagickCore/option.c:2183 (lower-case keys) -> MhStatisticType
 STATISTICS = {"undefined": 0, "contrast": 10, "gradient": 1, "maximum": 2, "mean": 3, "median": 4,
@@ -233,6 +237,15 @@ PROTOTYPES = [
     ("MagickHipEqualizeImage", ctypes.c_int, [_P(MhImage)]),
     ("MagickHipCLAHEImage", ctypes.c_int, [_P(MhImage), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
                                            ctypes.c_double]),
+    ("MagickHipBilevelImage", ctypes.c_int, [_P(MhImage), ctypes.c_double]),
+    ("MagickHipAutoThresholdImage", ctypes.c_int, [_P(MhImage), ctypes.c_int, _P(ctypes.c_double)]),
+    ("MhAutoThresholdFromHistogram", ctypes.c_int, [_P(ctypes.c_double), ctypes.c_int, _P(ctypes.c_double)]),
+    ("MagickHipAdaptiveThresholdImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_size_t, ctypes.c_size_t,
+                                                       ctypes.c_double]),
+    ("MagickHipBlackThresholdImage", ctypes.c_int, [_P(MhImage), _P(ctypes.c_double)]),
+    ("MagickHipWhiteThresholdImage", ctypes.c_int, [_P(MhImage), _P(ctypes.c_double)]),
+    ("MagickHipRangeThresholdImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double]),
     ("MagickHipTransformImageColorspace", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipGrayscaleImage", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipImportImagePixels", ctypes.c_int, [_P(MhImage), ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_size_t,

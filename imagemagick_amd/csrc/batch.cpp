@@ -196,6 +196,14 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
         case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
           p.histogram=true;
           break;
+        case MH_OP_THRESHOLD: case MH_OP_AUTO_THRESHOLD:
+          break;
+        case MH_OP_ADAPTIVE_THRESHOLD:
+          // width and height are size_t arguments of the call
+          for (int k=0; k < 2; k++)
+            if (!(p.op.args[k] >= 0.0) || (p.op.args[k] > 4294967295.0))
+              return fail(MH_BAD_ARGUMENT,"operator %zu: adaptive threshold argument %d is %g",i,k,p.op.args[k]);
+          break;
         default:
           return fail(MH_BAD_ARGUMENT,"operator %zu: unknown kind %u",i,p.op.kind);
       }
@@ -233,6 +241,10 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       return MagickHipEqualizeImage(&cur.image);
     case MH_OP_CLAHE:
       return MagickHipCLAHEImage(&cur.image,(size_t) op.args[0],(size_t) op.args[1],(size_t) op.args[2],op.args[3]);
+    case MH_OP_THRESHOLD:
+      return MagickHipBilevelImage(&cur.image,op.args[0]);
+    case MH_OP_AUTO_THRESHOLD:
+      return MagickHipAutoThresholdImage(&cur.image,(MhAutoThresholdMethod) (int) op.args[0],nullptr);
     default:
       break;
   }
@@ -275,6 +287,9 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       break;
     case MH_OP_KUWAHARA:
       status=MagickHipKuwaharaImage(&cur.image,&next,op.args[0],op.args[1]);
+      break;
+    case MH_OP_ADAPTIVE_THRESHOLD:
+      status=MagickHipAdaptiveThresholdImage(&cur.image,&next,(size_t) op.args[0],(size_t) op.args[1],op.args[2]);
       break;
     case MH_OP_MORPHOLOGY:
       status=MagickHipMorphologyImage(&cur.image,&next,(MhMorphologyMethod) (int) op.args[0],
@@ -859,6 +874,10 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
         return fail(MH_UNSUPPORTED,"ShardedImage: resize changes the geometry");
       if (p.op.kind == MH_OP_CLAHE)
         return fail(MH_UNSUPPORTED,"ShardedImage: CLAHEImage's tile grid belongs to the whole frame");
+      if ((p.op.kind == MH_OP_THRESHOLD) || (p.op.kind == MH_OP_AUTO_THRESHOLD) ||
+          (p.op.kind == MH_OP_ADAPTIVE_THRESHOLD))
+        return fail(MH_UNSUPPORTED,"ShardedImage: the threshold operators are not sharded (AutoThresholdImage needs the "
+          "bands' counts all-reduced, AdaptiveThresholdImage a halo)");
       if (p.reach == (size_t) -1)
         return fail(MH_UNSUPPORTED,"ShardedImage: iterate-until-convergence has no halo bound");
       reach=p.reach > reach ? p.reach : reach;

@@ -441,6 +441,21 @@ MhStatus launch_kuwahara(const View &blurred,const View &original,const View &ds
 // (clahe.hip).  clahe_check: what launch_clahe would decline, asked before the frame is converted
 MhStatus clahe_check(const View &img,size_t width,size_t height,size_t number_bins,double clip_limit);
 MhStatus launch_clahe(const View &img,size_t width,size_t height,size_t number_bins,double clip_limit);
+// The threshold operators (threshold.hip), in place: desc supplies the traits, the channel mask and
+// what GetPixelIntensity needs.  thresholds: MH_MAX_CHANNELS values, per stored channel
+MhStatus launch_bilevel(const View &img,double threshold,const MhImage *desc);
+MhStatus launch_black_white_threshold(const View &img,bool white,const double *thresholds,const MhImage *desc);
+// low_scale = QuantumRange*PerceptibleReciprocal(low_white-low_black), high_scale likewise for
+// high_black-high_white: the left product of the ramps, which does not depend on the pixel
+MhStatus launch_range_threshold(const View &img,double low_black,double low_white,double high_white,
+  double high_black,double low_scale,double high_scale,const MhImage *desc);
+// 256 counts of ScaleQuantumToChar(ClampToQuantum(intensity)); counts_device is zeroed here
+MhStatus launch_threshold_histogram(const View &img,const MhImage *desc,unsigned long long *counts_device);
+// AdaptiveThresholdImage, width and height >= 1.  adaptive_threshold_check: what the launcher would
+// decline (MH_UNSUPPORTED: a window over the kernel's limits), asked before the destination is touched
+MhStatus adaptive_threshold_check(const View &src,size_t width,size_t height);
+MhStatus launch_adaptive_threshold(const View &src,const View &dst,size_t width,size_t height,double bias,
+  uint32_t copy_mask);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

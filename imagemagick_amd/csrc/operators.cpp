@@ -1091,6 +1091,32 @@ MH_API MhStatus MagickHipStatisticImage(const MhImage *image,MhImage *statistic_
   return pair.commit();
 }
 
+// AdaptiveThresholdImage, threshold.c:182-361
+MH_API MhStatus MagickHipAdaptiveThresholdImage(const MhImage *image,MhImage *threshold_image,size_t width,
+  size_t height,double bias)
+{
+  MH_TRY(gate_pair(image,threshold_image,"AdaptiveThresholdImage",true));
+  Pair pair;
+  MH_TRY(pair.open(image,threshold_image));
+  if ((width == 0) || (height == 0))
+    {
+      // threshold.c:219-220: the clone as it is
+      MH_TRY(launch_copy(pair.src.view,pair.dst.view));
+      return pair.commit();
+    }
+  // decided before the destination is touched
+  MH_TRY(adaptive_threshold_check(pair.src.view,width,height));
+  // threshold.c:279-286: a channel without a trait on either side keeps the clone's sample, one whose
+  // trait in the destination carries Copy takes the centre sample: the source sample both times
+  uint32_t copy_mask=0;
+  for (uint32_t c=0; c < image->number_channels; c++)
+    if ((image->channel_traits[c] == MH_TRAIT_UNDEFINED) || (threshold_image->channel_traits[c] == MH_TRAIT_UNDEFINED) ||
+        ((threshold_image->channel_traits[c] & MH_TRAIT_COPY) != 0))
+      copy_mask|=1u << c;
+  MH_TRY(launch_adaptive_threshold(pair.src.view,pair.dst.view,width,height,bias,copy_mask));
+  return pair.commit();
+}
+
 MH_API MhStatus MagickHipBilateralBlurImage(const MhImage *image,MhImage *blur_image,size_t width,
   size_t height,double intensity_sigma,double spatial_sigma)
 {

@@ -706,4 +706,243 @@ MH_API MhStatus MagickHipFunctionImage(MhImage *image,MhFunction function,
   return io.img.commit();
 }
 
+// ------------------------------------------------------------------ threshold.c
+// The frames the reference's IsGrayColorspace() holds for gray: fewer than three colour channels
+// are laid out that way whatever the descriptor's colourspace says (pixel_intensity.inc.hpp).
+static bool threshold_gray_frame(const MhImage *image)
+{
+  const uint32_t colours=image->number_channels-(image->alpha_offset >= 0 ? 1u : 0u);
+  return (image->colorspace == MH_COLORSPACE_GRAY) || (image->colorspace == MH_COLORSPACE_LINEARGRAY) ||
+    (colours < 3);
+}
+
+// KapurThreshold, threshold.c:392-489
+static double kapur_threshold(const double *histogram)
+{
+  double black_entropy[256],cumulative_histogram[256],white_entropy[256];
+  cumulative_histogram[0]=histogram[0];
+  for (int i=1; i <= 255; i++)
+    cumulative_histogram[i]=cumulative_histogram[i-1]+histogram[i];
+  const double epsilon=2.22507385850720140E-308;      // MagickMinimumValue, magick-type.h:116
+  for (int j=0; j <= 255; j++)
+    {
+      black_entropy[j]=0.0;
+      if (cumulative_histogram[j] > epsilon)
+        {
+          double entropy=0.0;
+          for (int i=0; i <= j; i++)
+            if (histogram[i] > epsilon)
+              entropy-=histogram[i]/cumulative_histogram[j]*log(histogram[i]/cumulative_histogram[j]);
+          black_entropy[j]=entropy;
+        }
+      white_entropy[j]=0.0;
+      if ((1.0-cumulative_histogram[j]) > epsilon)
+        {
+          double entropy=0.0;
+          for (int i=j+1; i <= 255; i++)
+            if (histogram[i] > epsilon)
+              entropy-=histogram[i]/(1.0-cumulative_histogram[j])*log(histogram[i]/(1.0-cumulative_histogram[j]));
+          white_entropy[j]=entropy;
+        }
+    }
+  double maximum_entropy=black_entropy[0]+white_entropy[0];
+  size_t threshold=0;
+  for (int j=1; j <= 255; j++)
+    if ((black_entropy[j]+white_entropy[j]) > maximum_entropy)
+      {
+        maximum_entropy=black_entropy[j]+white_entropy[j];
+        threshold=(size_t) j;
+      }
+  return 100.0*threshold/255;
+}
+
+// OTSUThreshold, threshold.c:491-568
+static double otsu_threshold(const double *histogram)
+{
+  double myu[256],omega[256],probability[256],sigma[256];
+  for (int i=0; i <= 255; i++)
+    probability[i]=histogram[i];
+  omega[0]=probability[0];
+  myu[0]=0.0;
+  for (int i=1; i <= 255; i++)
+    {
+      omega[i]=omega[i-1]+probability[i];
+      myu[i]=myu[i-1]+i*probability[i];
+    }
+  double threshold=0,max_sigma=0.0;
+  for (int i=0; i < 255; i++)
+    {
+      sigma[i]=0.0;
+      if ((omega[i] != 0.0) && (omega[i] != 1.0))
+        sigma[i]=pow(myu[255]*omega[i]-myu[i],2.0)/(omega[i]*(1.0-omega[i]));
+      if (sigma[i] > max_sigma)
+        {
+          max_sigma=sigma[i];
+          threshold=(double) i;
+        }
+    }
+  return 100.0*threshold/255;
+}
+
+// TriangleThreshold, threshold.c:570-658
+static double triangle_threshold(const double *histogram)
+{
+  ssize_t start=0,end=0,max=0,threshold=0;
+  for (ssize_t i=0; i <= 255; i++)
+    if (histogram[i] > 0.0)
+      {
+        start=i;
+        break;
+      }
+  for (ssize_t i=255; i >= 0; i--)
+    if (histogram[i] > 0.0)
+      {
+        end=i;
+        break;
+      }
+  double count=0.0;
+  for (ssize_t i=0; i <= 255; i++)
+    if (histogram[i] > count)
+      {
+        max=i;
+        count=histogram[i];
+      }
+  const double x1=(double) max,y1=histogram[max];
+  double x2=(double) end;
+  if ((max-start) >= (end-max))
+    x2=(double) start;
+  const double y2=0.0;
+  const double a=y1-y2,b=x2-x1;
+  const double c=(-1.0)*(a*x1+b*y1);
+  const double inverse_ratio=1.0/sqrt(a*a+b*b+c*c);
+  double max_distance=0.0;
+  if (x2 == (double) start)
+    for (ssize_t i=start; i < max; i++)
+      {
+        const double segment=inverse_ratio*(a*i+b*histogram[i]+c);
+        const double distance=sqrt(segment*segment);
+        if ((distance > max_distance) && (segment > 0.0))
+          {
+            threshold=i;
+            max_distance=distance;
+          }
+      }
+  else
+    for (ssize_t i=end; i > max; i--)
+      {
+        const double segment=inverse_ratio*(a*i+b*histogram[i]+c);
+        const double distance=sqrt(segment*segment);
+        if ((distance > max_distance) && (segment < 0.0))
+          {
+            threshold=i;
+            max_distance=distance;
+          }
+      }
+  return 100.0*threshold/255;
+}
+
+// AutoThresholdImage's normalisation and selection, threshold.c:718-748, on the host
+MH_API MhStatus MhAutoThresholdFromHistogram(const double counts[256],MhAutoThresholdMethod method,
+  double *threshold_percent)
+{
+  if ((counts == nullptr) || (threshold_percent == nullptr))
+    return fail(MH_BAD_ARGUMENT,"AutoThresholdFromHistogram: null argument");
+  double histogram[256],sum=0.0;
+  for (int i=0; i <= 255; i++)
+    sum+=counts[i];
+  const double gamma=perceptible_reciprocal(sum);
+  for (int i=0; i <= 255; i++)
+    histogram[i]=gamma*counts[i];
+  switch (method)
+  {
+    case MH_AUTO_THRESHOLD_KAPUR: *threshold_percent=kapur_threshold(histogram); break;
+    case MH_AUTO_THRESHOLD_TRIANGLE: *threshold_percent=triangle_threshold(histogram); break;
+    case MH_AUTO_THRESHOLD_OTSU: default: *threshold_percent=otsu_threshold(histogram); break;
+  }
+  return MH_OK;
+}
+
+// BilevelImage on an open frame: threshold.c:828-829 retags a frame outside the gray colourspaces
+// as sRGB before the intensity is formed
+static MhStatus bilevel_view(const View &view,MhImage *image,double threshold)
+{
+  if (!threshold_gray_frame(image))
+    image->colorspace=MH_COLORSPACE_SRGB;
+  return launch_bilevel(view,threshold,image);
+}
+
+MH_API MhStatus MagickHipBilevelImage(MhImage *image,double threshold)
+{
+  MH_TRY(check_image(image,"BilevelImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(bilevel_view(io.img.view,image,threshold));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipAutoThresholdImage(MhImage *image,MhAutoThresholdMethod method,double *threshold_percent)
+{
+  MH_TRY(check_image(image,"AutoThresholdImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  const View &view=io.img.view;
+  Temp table;
+  MH_TRY(table.alloc(view.device,256*sizeof(unsigned long long),view.stream));
+  MH_TRY(launch_threshold_histogram(view,image,table.as<unsigned long long>()));
+  unsigned long long host[256];
+  MH_HIP(hipMemcpyAsync(host,table.ptr,sizeof(host),hipMemcpyDeviceToHost,view.stream));
+  MH_HIP(hipStreamSynchronize(view.stream));
+  double counts[256],percent=0.0;
+  for (int i=0; i < 256; i++)
+    counts[i]=(double) host[i];          // the reference counts in doubles: exact below 2^53
+  MH_TRY(MhAutoThresholdFromHistogram(counts,method,&percent));
+  if (threshold_percent != nullptr)
+    *threshold_percent=percent;
+  MH_TRY(bilevel_view(view,image,kQuantumRange*percent/100.0));
+  return io.img.commit();
+}
+
+// Black / White / RangeThresholdImage re-lay a gray frame out as sRGB (threshold.c:961, :2401, :2552)
+static MhStatus threshold_colour_frame(const MhImage *image,const char *what)
+{
+  MH_TRY(check_image(image,what));
+  if (threshold_gray_frame(image))
+    return fail(MH_UNSUPPORTED,"%s: the reference re-lays a gray frame out as sRGB",what);
+  return MH_OK;
+}
+
+MH_API MhStatus MagickHipBlackThresholdImage(MhImage *image,const double thresholds[MH_MAX_CHANNELS])
+{
+  MH_TRY(threshold_colour_frame(image,"BlackThresholdImage"));
+  if (thresholds == nullptr)
+    return fail(MH_BAD_ARGUMENT,"BlackThresholdImage: null thresholds");
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(launch_black_white_threshold(io.img.view,false,thresholds,image));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipWhiteThresholdImage(MhImage *image,const double thresholds[MH_MAX_CHANNELS])
+{
+  MH_TRY(threshold_colour_frame(image,"WhiteThresholdImage"));
+  if (thresholds == nullptr)
+    return fail(MH_BAD_ARGUMENT,"WhiteThresholdImage: null thresholds");
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(launch_black_white_threshold(io.img.view,true,thresholds,image));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipRangeThresholdImage(MhImage *image,double low_black,double low_white,double high_white,
+  double high_black)
+{
+  MH_TRY(threshold_colour_frame(image,"RangeThresholdImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(launch_range_threshold(io.img.view,low_black,low_white,high_white,high_black,
+    kQuantumRange*perceptible_reciprocal(low_white-low_black),
+    kQuantumRange*perceptible_reciprocal(high_black-high_white),image));
+  return io.img.commit();
+}
+
 } // extern "C"

@@ -628,6 +628,71 @@ MH_API MhStatus MagickHipEqualizeImage(MhImage *image);
 MH_API MhStatus MagickHipCLAHEImage(MhImage *image,size_t width,size_t height,size_t number_bins,
   double clip_limit);
 
+/* ---- The threshold operators, MagickCore/threshold.c (no accelerate hook in the reference).
+   Every result is a comparison, so all of them are bit-identical to the reference in both
+   precision modes, on Q16 and float Quantum, 1-4 channels, host and device memory.  NaN and
+   infinite samples are outside the contract.
+   The pointwise calls form `pixel` = GetPixelIntensity (MhImage::intensity, colorspace) once per
+   pixel; with a channel_mask other than MH_ALL_CHANNELS every channel is decided by its own sample
+   instead.  Only channels whose trait carries MH_TRAIT_UPDATE are written. */
+
+/* AutoThresholdMethod, MagickCore/threshold.h:25-31 */
+typedef enum
+{
+  MH_AUTO_THRESHOLD_UNDEFINED = 0,
+  MH_AUTO_THRESHOLD_KAPUR = 1,
+  MH_AUTO_THRESHOLD_OTSU = 2,
+  MH_AUTO_THRESHOLD_TRIANGLE = 3
+} MhAutoThresholdMethod;
+
+/* BilevelImage(image,threshold), threshold.c:805-896, in place: pixel <= threshold ? 0 : QuantumRange.
+   A frame outside the gray colourspaces is retagged sRGB first, as SetImageColorspace does there:
+   image->colorspace ends at MH_COLORSPACE_SRGB. */
+MH_API MhStatus MagickHipBilevelImage(MhImage *image,double threshold);
+
+/* AutoThresholdImage(image,method), threshold.c:660-762, in place: 256 counts of
+   ScaleQuantumToChar(ClampToQuantum(intensity)) gathered on the device, the selection
+   (MhAutoThresholdFromHistogram) on the host, then BilevelImage at QuantumRange*percent/100.
+   *threshold_percent (optional) receives the value the reference formats into the
+   "auto-threshold:threshold" property.  A method outside the three takes OTSU, as the reference's
+   `default:` does. */
+MH_API MhStatus MagickHipAutoThresholdImage(MhImage *image,MhAutoThresholdMethod method,
+  double *threshold_percent);
+
+/* The host half of AutoThresholdImage, threshold.c:392-658 and :718-748: normalisation by
+   PerceptibleReciprocal(sum) and the Kapur / OTSU / Triangle selection, operation for operation
+   (log, pow and sqrt of the host's libm).  counts: the 256 bins.  No device is touched. */
+MH_API MhStatus MhAutoThresholdFromHistogram(const double counts[256],MhAutoThresholdMethod method,
+  double *threshold_percent);
+
+/* AdaptiveThresholdImage(image,width,height,bias), threshold.c:182-361: threshold_image(x,y) =
+   centre <= sum/(width*height)+bias ? 0 : QuantumRange over the window of columns x-width/2 ...
+   x-width/2+width-1 and rows y-height/2 ... y-height/2+height-1, edge-clamped.  Channels whose
+   trait in threshold_image carries MH_TRAIT_COPY (or is undefined on either side) receive the
+   source sample.  width == 0 or height == 0: a copy of the source.
+   Q16: exact integer window sums.  Float Quantum: the reference's running sum, statement for
+   statement, one sequential chain per row and channel (slower).
+   MH_UNSUPPORTED (threshold_image untouched; the CPU path runs): Q16 with width > 257 (a strip of
+   512 input columns keeps at least 256 outputs: width <= 512/2+1) or height > 65537 (a column sum
+   of height samples fits 32 bits: height*65535 < 2^32); float Quantum with a side above 2^20; a
+   frame side above 2^30-1. */
+MH_API MhStatus MagickHipAdaptiveThresholdImage(const MhImage *image,MhImage *threshold_image,size_t width,
+  size_t height,double bias);
+
+/* BlackThresholdImage :927-1058 (pixel < threshold: 0) and WhiteThresholdImage :2518-2648
+   (pixel > threshold: QuantumRange), in place.  thresholds[c]: the threshold of the channel stored
+   at offset c, in Quantum units; the geometry string and its percent flag stay with the caller.
+   MH_UNSUPPORTED (image untouched): a frame in a gray colourspace or with fewer than three colour
+   channels, which the reference re-lays out as sRGB first. */
+MH_API MhStatus MagickHipBlackThresholdImage(MhImage *image,const double thresholds[MH_MAX_CHANNELS]);
+MH_API MhStatus MagickHipWhiteThresholdImage(MhImage *image,const double thresholds[MH_MAX_CHANNELS]);
+
+/* RangeThresholdImage(image,low_black,low_white,high_white,high_black), threshold.c:2377-2487, in
+   place, branch for branch; the ramps are ClampToQuantum(QuantumRange*PerceptibleReciprocal(d)*
+   (pixel-low)) in that order in fp64.  MH_UNSUPPORTED: gray frames, as above. */
+MH_API MhStatus MagickHipRangeThresholdImage(MhImage *image,double low_black,double low_white,
+  double high_white,double high_black);
+
 /* TransformImageColorspace, colorspace.c:1751 — sRGB <-> linear RGB / Lab / XYZ.
    On success image->colorspace is updated. */
 MH_API MhStatus MagickHipTransformImageColorspace(MhImage *image,MhColorspace colorspace);
@@ -771,9 +836,14 @@ typedef enum
   MH_OP_BILATERAL_BLUR = 10,   /* args: width, height, intensity_sigma, spatial_sigma */
   MH_OP_SELECTIVE_BLUR = 11,   /* args: radius, sigma, threshold */
   MH_OP_KUWAHARA = 12,         /* args: radius, sigma */
-  MH_OP_CLAHE = 13             /* args: width, height, number_bins, clip_limit; MagickHipBatchImages
+  MH_OP_CLAHE = 13,            /* args: width, height, number_bins, clip_limit; MagickHipBatchImages
                                   only: MagickHipShardedImage returns MH_UNSUPPORTED for it, the
                                   tile grid belongs to the whole frame, not to a row band */
+  MH_OP_THRESHOLD = 14,        /* args: threshold (BilevelImage) */
+  MH_OP_AUTO_THRESHOLD = 15,   /* args: MhAutoThresholdMethod */
+  MH_OP_ADAPTIVE_THRESHOLD = 16 /* args: width, height, bias.  These three: MagickHipBatchImages only;
+                                  MagickHipShardedImage returns MH_UNSUPPORTED (AutoThresholdImage would
+                                  need the bands' counts all-reduced, AdaptiveThresholdImage a halo) */
 } MhOperatorKind;
 
 typedef struct MhOperator

@@ -43,6 +43,9 @@
 #include "MagickCore/composite.h"
 #include "MagickCore/morphology.h"
 #include "MagickCore/profile.h"
+#include "MagickCore/property.h"
+#include "MagickCore/magick.h"
+#include "MagickCore/threshold.h"
 
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 
@@ -1053,6 +1056,103 @@ MagickPrivate MagickBooleanType AccelerateCLAHEImage(Image *image,const size_t w
   if (SetResidentImageColorspace(call.library,image,LabColorspace,exception) == MagickFalse)
     return(MagickFalse);
   return(SetResidentImageColorspace(call.library,image,colorspace,exception));
+}
+
+/*
+  The threshold operators' call sites (the shim's own hooks, shim/patch_hooks.py): the top of
+  AdaptiveThresholdImage (threshold.c:216), BilevelImage (:826) and AutoThresholdImage (:691).  The
+  library sees the pixels, the traits, the channel mask, the intensity method and the colourspace;
+  what it cannot see is gated here: the storage class, a virtual-pixel method other than Undefined
+  or Edge (AdaptiveThresholdImage reads its window through the virtual pixels) and the read, write
+  and composite masks (IsLayoutAcceleratable).  Any colourspace: the operators compare samples, and
+  GetPixelIntensity asks the colourspace only whether it is linear (pixel.c:2356-2455), as the
+  library does.  A declined call has touched nothing.
+*/
+MagickPrivate Image *AccelerateAdaptiveThresholdImage(const Image *image,const size_t width,
+  const size_t height,const double bias,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *threshold_image;
+
+  if (IsLayoutAcceleratable(image) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  if (BeginHipCall(&call,image,image->columns,image->rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  threshold_image=EndHipCall(&call,call.library->AdaptiveThresholdImage(&call.source,&call.destination,
+    width,height,bias));
+  if (threshold_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));      /* a window over the kernels' limits: the CPU path */
+  threshold_image->type=image->type;                /* threshold.c:355 */
+  HipAccepted(image);
+  return(threshold_image);
+}
+
+/* BilevelImage retags a frame outside the gray colourspaces as sRGB (threshold.c:828-829) */
+static MagickBooleanType RetagThresholdedImage(HipLibrary *library,Image *image,ExceptionInfo *exception)
+{
+  if ((IsGrayColorspace(image->colorspace) != MagickFalse) || (image->colorspace == sRGBColorspace))
+    return(MagickTrue);
+  return(SetResidentImageColorspace(library,image,sRGBColorspace,exception));
+}
+
+MagickPrivate MagickBooleanType AccelerateBilevelImage(Image *image,const double threshold,
+  ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  MhStatus
+    status;
+
+  if (IsLayoutAcceleratable(image) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (BeginHipCall(&call,image,0,0,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  status=call.library->BilevelImage(&call.source,threshold);
+  (void) EndHipCall(&call,status);
+  if (status != MH_OK)
+    return(HipDeclined(image,MagickFalse));
+  MarkDeviceCopyNewer(image);
+  HipAccepted(image);
+  return(RetagThresholdedImage(call.library,image,exception));
+}
+
+MagickPrivate MagickBooleanType AccelerateAutoThresholdImage(Image *image,
+  const AutoThresholdMethod method,ExceptionInfo *exception)
+{
+  char
+    property[MagickPathExtent];
+
+  double
+    threshold;
+
+  HipCall
+    call;
+
+  MhStatus
+    status;
+
+  if (IsLayoutAcceleratable(image) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (BeginHipCall(&call,image,0,0,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  /* AutoThresholdMethod and MhAutoThresholdMethod share their values (threshold.h:25-31) */
+  threshold=0.0;
+  status=call.library->AutoThresholdImage(&call.source,(MhAutoThresholdMethod) method,&threshold);
+  (void) EndHipCall(&call,status);
+  if (status != MH_OK)
+    return(HipDeclined(image,MagickFalse));
+  MarkDeviceCopyNewer(image);
+  HipAccepted(image);
+  /* threshold.c:757-760 */
+  (void) FormatLocaleString(property,MagickPathExtent,"%g%%",threshold);
+  (void) SetImageProperty(image,"auto-threshold:threshold",property,exception);
+  if (IsStringTrue(GetImageArtifact(image,"auto-threshold:verbose")) != MagickFalse)
+    (void) FormatLocaleFile(stdout,"%.*g%%\n",GetMagickPrecision(),threshold);
+  return(RetagThresholdedImage(call.library,image,exception));
 }
 
 /* DespeckleImage's call site: effect.c:1342-1346 */

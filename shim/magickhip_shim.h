@@ -50,6 +50,9 @@ typedef struct _HipLibrary
   MhStatus (*SelectiveBlurImage)(const MhImage *,MhImage *,double,double,double);
   MhStatus (*KuwaharaImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*CLAHEImage)(MhImage *,size_t,size_t,size_t,double);
+  MhStatus (*BilevelImage)(MhImage *,double);
+  MhStatus (*AutoThresholdImage)(MhImage *,MhAutoThresholdMethod,double *);
+  MhStatus (*AdaptiveThresholdImage)(const MhImage *,MhImage *,size_t,size_t,double);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

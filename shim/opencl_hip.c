@@ -179,6 +179,9 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(SelectiveBlurImage,"MagickHipSelectiveBlurImage");
   MH_RESOLVE(KuwaharaImage,"MagickHipKuwaharaImage");
   MH_RESOLVE(CLAHEImage,"MagickHipCLAHEImage");
+  MH_RESOLVE(BilevelImage,"MagickHipBilevelImage");
+  MH_RESOLVE(AutoThresholdImage,"MagickHipAutoThresholdImage");
+  MH_RESOLVE(AdaptiveThresholdImage,"MagickHipAdaptiveThresholdImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Generates, at build time, copies of six MagickCore sources with the accelerate call
+"""Generates, at build time, copies of seven MagickCore sources with the accelerate call
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
-StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage and CLAHEImage lack altogether.  Each hook is the reference's own three-line idiom
+StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage, CLAHEImage, AdaptiveThresholdImage, BilevelImage
+and AutoThresholdImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -54,6 +55,16 @@ ENHANCE_PROTOTYPE = '''
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 extern MagickPrivate MagickBooleanType AccelerateCLAHEImage(Image *,const size_t,const size_t,
   const size_t,const double,ExceptionInfo *);
+#endif
+'''
+
+THRESHOLD_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate Image *AccelerateAdaptiveThresholdImage(const Image *,const size_t,const size_t,
+  const double,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateBilevelImage(Image *,const double,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateAutoThresholdImage(Image *,const AutoThresholdMethod,
+  ExceptionInfo *);
 #endif
 '''
 
@@ -186,12 +197,37 @@ def statistic(text):
     return once(text, anchor, hook, "statistic.c")
 
 
+def threshold(text):
+    # AdaptiveThresholdImage, BilevelImage and AutoThresholdImage have no accelerate hook in the
+    # reference: one at the top of each, in front of the first statement behind the asserts
+    text = after_includes(text, THRESHOLD_PROTOTYPE)
+    anchor = "  threshold_image=CloneImage(image,0,0,MagickTrue,exception);\n"
+    text = in_function(text, "MagickExport Image *AdaptiveThresholdImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  threshold_image=AccelerateAdaptiveThresholdImage(image,width,height,bias,exception);
+  if (threshold_image != (Image *) NULL)
+    return(threshold_image);
+#endif
+''' + anchor, "threshold.c")
+    anchor = "  if (SetImageStorageClass(image,DirectClass,exception) == MagickFalse)\n"
+    text = in_function(text, "MagickExport MagickBooleanType BilevelImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  if (AccelerateBilevelImage(image,threshold,exception) != MagickFalse)
+    return(MagickTrue);
+#endif
+''' + anchor, "threshold.c")
+    anchor = "  histogram=(double *) AcquireQuantumMemory(MaxIntensity+1UL,\n    sizeof(*histogram));\n"
+    return in_function(text, "MagickExport MagickBooleanType AutoThresholdImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  if (AccelerateAutoThresholdImage(image,method,exception) != MagickFalse)
+    return(MagickTrue);
+#endif
+''' + anchor, "threshold.c")
+
+
 def main():
     source, out = sys.argv[1], sys.argv[2]
     os.makedirs(out, exist_ok=True)
     for name, fn in (("morphology.c", morphology), ("effect.c", effect), ("enhance.c", enhance),
                      ("colorspace.c", colorspace), ("visual-effects.c", visual_effects),
-                     ("statistic.c", statistic)):
+                     ("statistic.c", statistic), ("threshold.c", threshold)):
         text = open(os.path.join(source, name), encoding="latin-1").read()
         patched = fn(text)
         with open(os.path.join(out, name), "w", encoding="latin-1") as f:
