@@ -145,6 +145,24 @@ struct HybridGeometry
 #define MH_HTRACE_MARK(id) do { } while (0)
 #endif
 
+// Diagnostic build only (-DMH_HYBRID_ITEMS, tools/hybrid_item_balance.py): lane 0 of wave 0 of EVERY workgroup
+// stamps the shader clock and the constant-rate clock when it starts and when it has left the walk:
+// trace[item][first cycles, last cycles, first ticks, last ticks].  The launch is one round of workgroups, one a CU:
+// it lasts as long as its slowest item.
+#ifdef MH_HYBRID_ITEMS
+#define MH_HITEM_STAMP(slot) \
+  do { \
+    const unsigned long long cycles=__builtin_readcyclecounter(),ticks=wall_clock64(); \
+    if ((args.trace != nullptr) && (tid == 0)) \
+      { \
+        args.trace[4*item+(slot)]=cycles; \
+        args.trace[4*item+2+(slot)]=ticks; \
+      } \
+  } while (0)
+#else
+#define MH_HITEM_STAMP(slot) do { } while (0)
+#endif
+
 template<int NC,int MODE>
 __global__ __launch_bounds__(1024)
 void blur_fused_hybrid_kernel(BlurExactArgs args)
@@ -193,6 +211,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   const int item=((int) blockIdx.x & 7)*args.items_per_xcd+((int) blockIdx.x >> 3);
   if (item >= items)
     return;
+  MH_HITEM_STAMP(0);
 #ifdef MH_HYBRID_TRACE
   const bool traced=(args.trace != nullptr) && (blockIdx.x < 4);
 #endif
@@ -311,6 +330,16 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // behind an s_waitcnt vmcnt(0) that also waits for the prefetched pixels: 9 such reloads cost
   // 0.25 ms per 8192^2 frame.)
   const bool stager=tid < G::FETCH_GROUPS;     // wave-uniform (FETCH_GROUPS is a multiple of 64)
+  // An EDGE item: its staged window hangs over the image's left or right edge (the first and the last strip, every
+  // segment of them), so some of its column groups are clamped.  Decided per ITEM — workgroup-uniform, a scalar
+  // branch — and not per lane: a stager is thread tid/GROUPS_PER_ROW's row, so every staging wave of an edge item
+  // holds groups inside and outside the image, and under a per-lane test ran the group loads AND the clamped loads
+  // in every iteration: 1.12-1.14 of an interior item's time, in a launch of one workgroup a CU in one round, which
+  // lasts as long as its slowest item.  Every thread of an edge item takes the clamped loads (1.02); an interior
+  // item's walk tests nothing per lane.  (Loading the group at clamp(xs, 0, W-4) and picking clamp(xs+i, 0, W-1) out
+  // of it with selects — two loads a thread — brought the edge items to 1.006, but its 24 selects and their branch in
+  // the middle of the staging chain cost every interior item 3 %: profiles/hybrid_item_balance.md.)
+  const bool edge_item=(xin0 < 0) || (xin0+4*G::GROUPS_PER_ROW > W);
   auto fetch=[&](int g,int srow,int sxg)
   {
     if (stager)
@@ -318,31 +347,34 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
         int y=in0+G::GROUP*(MH_HKNOCKED(256) ? 0 : g)+srow;
         y=y < 0 ? 0 : (y > H-1 ? H-1 : y);       // the intermediate's edge clamp (cache.c:2663-2679)
         const int xs=xin0+4*sxg;
-        if ((MODE == MFMA_PLAIN3) && (xs >= 0) && (xs+3 <= W-1))
+        if (__builtin_expect(!edge_item,1))
           {
-            // four RGB pixels = 24 contiguous bytes, re-cut into pixels
-            const uint16_t *at=args.src+pixel_index(y,W,xs)*3;
-            const LooseDword *words=reinterpret_cast<const LooseDword *>(at);
-            const uint2 a=make_uint2(words[0],words[1]),b=make_uint2(words[2],words[3]),c=make_uint2(words[4],words[5]);
-            raw[0]=make_uint2(a.x,a.y & 0xffffu);
-            raw[1]=make_uint2((a.y >> 16) | (b.x << 16),b.x >> 16);
-            raw[2]=make_uint2(b.y,c.x & 0xffffu);
-            raw[3]=make_uint2((c.x >> 16) | (c.y << 16),c.y >> 16);
-          }
-        else if ((MODE != MFMA_PLAIN3) && (xs >= 0) && (xs+3 <= W-1))
-          {
-            typedef unsigned LooseQuad __attribute__((ext_vector_type(4),aligned(8)));
-            const LooseQuad *at=reinterpret_cast<const LooseQuad *>(args.src+pixel_index(y,W,xs)*4);
-            const LooseQuad a=at[0],b=at[1];
-            raw[0]=make_uint2(a[0],a[1]);
-            raw[1]=make_uint2(a[2],a[3]);
-            raw[2]=make_uint2(b[0],b[1]);
-            raw[3]=make_uint2(b[2],b[3]);
+            if constexpr (MODE == MFMA_PLAIN3)
+              {
+                // four RGB pixels = 24 contiguous bytes, re-cut into pixels
+                const uint16_t *at=args.src+pixel_index(y,W,xs)*3;
+                const LooseDword *words=reinterpret_cast<const LooseDword *>(at);
+                const uint2 a=make_uint2(words[0],words[1]),b=make_uint2(words[2],words[3]),c=make_uint2(words[4],words[5]);
+                raw[0]=make_uint2(a.x,a.y & 0xffffu);
+                raw[1]=make_uint2((a.y >> 16) | (b.x << 16),b.x >> 16);
+                raw[2]=make_uint2(b.y,c.x & 0xffffu);
+                raw[3]=make_uint2((c.x >> 16) | (c.y << 16),c.y >> 16);
+              }
+            else
+              {
+                typedef unsigned LooseQuad __attribute__((ext_vector_type(4),aligned(8)));
+                const LooseQuad *at=reinterpret_cast<const LooseQuad *>(args.src+pixel_index(y,W,xs)*4);
+                const LooseQuad a=at[0],b=at[1];
+                raw[0]=make_uint2(a[0],a[1]);
+                raw[1]=make_uint2(a[2],a[3]);
+                raw[2]=make_uint2(b[0],b[1]);
+                raw[3]=make_uint2(b[2],b[3]);
+              }
           }
         else
           {
-            // (the strips at the left and right image edges only; opaque to the optimiser so that
-            // the four clamped columns are not kept in registers across the whole walk)
+            // (opaque to the optimiser so that the four clamped columns are not kept in registers across the whole
+            // walk)
             int edge=xs;
             asm volatile("" : "+v"(edge));
 #pragma unroll
@@ -703,6 +735,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       MH_HTRACE_MARK(8);
       ring_group=ring_group+1 == G::NR ? 0 : ring_group+1;
     }
+  MH_HITEM_STAMP(1);
   if ((args.recomputed != nullptr) && (recomputed != 0u) && (lane == 0))     // a wave-uniform count
     atomicAdd(args.recomputed,(unsigned long long) recomputed);
 }
@@ -745,6 +778,15 @@ static MhStatus launch_hybrid_typed(const View &src,BlurExactArgs &args)
       MH_HIP(hipMemsetAsync(args.trace,0,trace_bytes,src.stream));
     }
 #endif
+#ifdef MH_HYBRID_ITEMS
+  const char *items_path=option("MAGICKHIP_HYBRID_ITEMS");
+  const size_t items_bytes=(size_t) items*4u*sizeof(unsigned long long);
+  if (items_path != nullptr)
+    {
+      MH_HIP(hipMalloc(reinterpret_cast<void **>(&args.trace),items_bytes));
+      MH_HIP(hipMemsetAsync(args.trace,0,items_bytes,src.stream));
+    }
+#endif
   {
     ProfileScope prof("blur_fused_hybrid",src.stream);
     hipLaunchKernelGGL((blur_fused_hybrid_kernel<NC,MODE>),dim3((unsigned) (8*args.items_per_xcd)),dim3(1024),lds,
@@ -761,6 +803,24 @@ static MhStatus launch_hybrid_typed(const View &src,BlurExactArgs &args)
       if (FILE *f=fopen(trace_path,"wb"))
         {
           fwrite(host.data(),1,trace_bytes,f);
+          fclose(f);
+        }
+      args.trace=nullptr;
+    }
+#endif
+#ifdef MH_HYBRID_ITEMS
+  if (args.trace != nullptr)
+    {
+      // the file: strips, segments, then the four stamps of every item (item = segment*strips + strip)
+      std::vector<unsigned long long> host(2+items_bytes/sizeof(unsigned long long));
+      host[0]=(unsigned long long) args.strips;
+      host[1]=(unsigned long long) args.segments;
+      MH_HIP(hipMemcpyAsync(host.data()+2,args.trace,items_bytes,hipMemcpyDeviceToHost,src.stream));
+      MH_HIP(hipStreamSynchronize(src.stream));
+      MH_HIP(hipFree(args.trace));
+      if (FILE *f=fopen(items_path,"wb"))
+        {
+          fwrite(host.data(),sizeof(unsigned long long),host.size(),f);
           fclose(f);
         }
       args.trace=nullptr;
