@@ -22,6 +22,9 @@ __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphol
            "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image", "clahe_image",
            "bilevel_image", "auto_threshold_image", "adaptive_threshold_image", "black_threshold_image",
            "white_threshold_image", "range_threshold_image", "auto_threshold_from_histogram",
+           "level_image", "levelize_image", "gamma_image", "negate_image", "sigmoidal_contrast_image",
+           "min_max_stretch_image", "auto_level_image", "linear_stretch_image", "normalize_image",
+           "brightness_contrast_image", "image_range", "gamma_lut", "levels_tables_built",
            "transform_image_colorspace", "wavelet_denoise_image", "despeckle_image", "statistic_image", "bilateral_blur_image", "selective_blur_image", "kuwahara_image", "local_contrast_image", "rotational_blur_image", "motion_blur_image", "gaussian_blur_image", "sharpen_image", "edge_image",
            "emboss_image", "import_image_pixels", "export_image_pixels", "contrast_image", "modulate_image", "grayscale_image", "function_image", "histogram", "apply_lut", "contrast_stretch_lut",
            "equalize_lut", "is_image_gray", "set_precision", "get_precision", "set_option", "get_option", "option",
@@ -593,6 +596,92 @@ def range_threshold_image(image, low_black, low_white, high_white, high_black):
     return image
 
 
+# ------------------------------------------------------------- the level operators
+def _in_place(name, image, *args):
+    lib = _lib.load()
+    _lib.check(getattr(lib, name)(ctypes.byref(image.descriptor()), *args))
+    return image
+
+
+def level_image(image, black_point, white_point, gamma=1.0):
+    """LevelImage(image, black_point, white_point, gamma), in place — MagickCore/enhance.c:2913;
+    the points in Quantum units."""
+    return _in_place("MagickHipLevelImage", image, float(black_point), float(white_point), float(gamma))
+
+
+def levelize_image(image, black_point, white_point, gamma=1.0):
+    """LevelizeImage, in place — MagickCore/enhance.c:3062."""
+    return _in_place("MagickHipLevelizeImage", image, float(black_point), float(white_point), float(gamma))
+
+
+def gamma_image(image, gamma):
+    """GammaImage(image, gamma), in place — MagickCore/enhance.c:2322 (image->gamma stays with the caller)."""
+    return _in_place("MagickHipGammaImage", image, float(gamma))
+
+
+def negate_image(image, grayscale=False):
+    """NegateImage(image, grayscale), in place — MagickCore/enhance.c:3940."""
+    return _in_place("MagickHipNegateImage", image, 1 if grayscale else 0)
+
+
+def sigmoidal_contrast_image(image, sharpen, contrast, midpoint):
+    """SigmoidalContrastImage(image, sharpen, contrast, midpoint), in place — MagickCore/enhance.c:4267;
+    midpoint in Quantum units."""
+    return _in_place("MagickHipSigmoidalContrastImage", image, 1 if sharpen else 0, float(contrast), float(midpoint))
+
+
+def min_max_stretch_image(image, black, white, gamma=1.0):
+    """MinMaxStretchImage(image, black, white, gamma), in place — MagickCore/histogram.c:927."""
+    return _in_place("MagickHipMinMaxStretchImage", image, float(black), float(white), float(gamma))
+
+
+def auto_level_image(image):
+    """AutoLevelImage, in place — MagickCore/enhance.c:187."""
+    return _in_place("MagickHipAutoLevelImage", image)
+
+
+def linear_stretch_image(image, black_point, white_point):
+    """LinearStretchImage(image, black_point, white_point), in place — MagickCore/enhance.c:3347; the
+    points are pixel counts.  Returns (image, black, white): the two histogram bins, which the
+    reference formats into the histogram:linear-stretch property."""
+    lib = _lib.load()
+    black, white = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(lib.MagickHipLinearStretchImage(ctypes.byref(image.descriptor()), float(black_point), float(white_point),
+                                               ctypes.byref(black), ctypes.byref(white)))
+    return image, black.value, white.value
+
+
+def normalize_image(image):
+    """NormalizeImage, in place — MagickCore/enhance.c:4130."""
+    return _in_place("MagickHipNormalizeImage", image)
+
+
+def brightness_contrast_image(image, brightness, contrast):
+    """BrightnessContrastImage(image, brightness, contrast), in place — MagickCore/enhance.c:224."""
+    return _in_place("MagickHipBrightnessContrastImage", image, float(brightness), float(contrast))
+
+
+def image_range(image):
+    """GetImageRange(image) -> (minimum, maximum) — MagickCore/statistic.c:1851, its row seed included."""
+    lib = _lib.load()
+    minimum, maximum = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    _lib.check(lib.MagickHipImageRange(ctypes.byref(image.descriptor()), ctypes.byref(minimum), ctypes.byref(maximum)))
+    return minimum.value, maximum.value
+
+
+def gamma_lut(gamma, quantum):
+    """GammaImage's 65536-entry map (MagickCore/enhance.c:2354-2362) in Quantum units.  No device is touched."""
+    lib = _lib.load()
+    lut = np.zeros(65536, dtype=np.float64)
+    _lib.check(lib.MhGammaLUT(float(gamma), quantum, lut.ctypes.data))
+    return lut
+
+
+def levels_tables_built():
+    """Tone-curve tables this process has built so far (a cache hit builds none)."""
+    return int(_lib.load().MhLevelsTablesBuilt())
+
+
 def transform_colorspace_contrast_stretch_image(image, colorspace, black_point, white_point):
     """TransformImageColorspace then ContrastStretchImage as one call (the two calls' results; a
     FAST sRGB -> Lab of an RGBA Q16 frame shares its pass over the pixels with the histogram)."""
@@ -761,8 +850,10 @@ def _operators(chain):
     ("equalize",), ("statistic", "Median", width, height), ("bilateralblur", width, height,
     intensity_sigma, spatial_sigma), ("selectiveblur", radius, sigma, threshold), ("kuwahara",
     radius, sigma), ("clahe", width, height, number_bins, clip_limit), ("threshold", threshold),
-    ("autothreshold", "OTSU"), ("adaptivethreshold", width, height, bias)] -> an MhOperator array (and
-    the byte strings it points at)."""
+    ("autothreshold", "OTSU"), ("adaptivethreshold", width, height, bias), ("level", black, white, gamma),
+    ("levelize", black, white, gamma), ("gamma", gamma), ("negate", grayscale), ("sigmoidalcontrast",
+    sharpen, contrast, midpoint), ("autolevel",), ("linearstretch", black_point, white_point),
+    ("normalize",)] -> an MhOperator array (and the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):

@@ -122,7 +122,9 @@ class MhBatchReport(ctypes.Structure):
 OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morphology": 5,
              "colorspace": 6, "contraststretch": 7, "equalize": 8, "statistic": 9,
              "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12, "clahe": 13,
-             "threshold": 14, "autothreshold": 15, "adaptivethreshold": 16}
+             "threshold": 14, "autothreshold": 15, "adaptivethreshold": 16,
+             "level": 17, "levelize": 18, "gamma": 19, "negate": 20, "sigmoidalcontrast": 21,
+             "autolevel": 22, "linearstretch": 23, "normalize": 24}
 
 # AutoThresholdMethod, MagickCore/threshold.h:25-31 (lower-case keys) -> MhAutoThresholdMethod
 AUTO_THRESHOLD = {"undefined": 0, "kapur": 1, "otsu": 2, "triangle": 3}
@@ -246,6 +248,20 @@ PROTOTYPES = [
     ("MagickHipWhiteThresholdImage", ctypes.c_int, [_P(MhImage), _P(ctypes.c_double)]),
     ("MagickHipRangeThresholdImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                     ctypes.c_double]),
+    ("MagickHipLevelImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    ("MagickHipLevelizeImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    ("MagickHipGammaImage", ctypes.c_int, [_P(MhImage), ctypes.c_double]),
+    ("MagickHipNegateImage", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
+    ("MagickHipSigmoidalContrastImage", ctypes.c_int, [_P(MhImage), ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    ("MagickHipImageRange", ctypes.c_int, [_P(MhImage), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    ("MagickHipMinMaxStretchImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    ("MagickHipAutoLevelImage", ctypes.c_int, [_P(MhImage)]),
+    ("MagickHipLinearStretchImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double,
+                                                   _P(ctypes.c_size_t), _P(ctypes.c_size_t)]),
+    ("MagickHipNormalizeImage", ctypes.c_int, [_P(MhImage)]),
+    ("MagickHipBrightnessContrastImage", ctypes.c_int, [_P(MhImage), ctypes.c_double, ctypes.c_double]),
+    ("MhGammaLUT", ctypes.c_int, [ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    ("MhLevelsTablesBuilt", ctypes.c_ulonglong, []),
     ("MagickHipTransformImageColorspace", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipGrayscaleImage", ctypes.c_int, [_P(MhImage), ctypes.c_int]),
     ("MagickHipImportImagePixels", ctypes.c_int, [_P(MhImage), ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_size_t,

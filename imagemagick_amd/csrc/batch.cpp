@@ -198,6 +198,9 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
           break;
         case MH_OP_THRESHOLD: case MH_OP_AUTO_THRESHOLD:
           break;
+        case MH_OP_LEVEL: case MH_OP_LEVELIZE: case MH_OP_GAMMA: case MH_OP_NEGATE: case MH_OP_SIGMOIDAL_CONTRAST:
+        case MH_OP_AUTO_LEVEL: case MH_OP_LINEAR_STRETCH: case MH_OP_NORMALIZE:
+          break;
         case MH_OP_ADAPTIVE_THRESHOLD:
           // width and height are size_t arguments of the call
           for (int k=0; k < 2; k++)
@@ -245,6 +248,22 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       return MagickHipBilevelImage(&cur.image,op.args[0]);
     case MH_OP_AUTO_THRESHOLD:
       return MagickHipAutoThresholdImage(&cur.image,(MhAutoThresholdMethod) (int) op.args[0],nullptr);
+    case MH_OP_LEVEL:
+      return MagickHipLevelImage(&cur.image,op.args[0],op.args[1],op.args[2]);
+    case MH_OP_LEVELIZE:
+      return MagickHipLevelizeImage(&cur.image,op.args[0],op.args[1],op.args[2]);
+    case MH_OP_GAMMA:
+      return MagickHipGammaImage(&cur.image,op.args[0]);
+    case MH_OP_NEGATE:
+      return MagickHipNegateImage(&cur.image,op.args[0] != 0.0 ? 1 : 0);
+    case MH_OP_SIGMOIDAL_CONTRAST:
+      return MagickHipSigmoidalContrastImage(&cur.image,op.args[0] != 0.0 ? 1 : 0,op.args[1],op.args[2]);
+    case MH_OP_AUTO_LEVEL:
+      return MagickHipAutoLevelImage(&cur.image);
+    case MH_OP_LINEAR_STRETCH:
+      return MagickHipLinearStretchImage(&cur.image,op.args[0],op.args[1],nullptr,nullptr);
+    case MH_OP_NORMALIZE:
+      return MagickHipNormalizeImage(&cur.image);
     default:
       break;
   }
@@ -878,6 +897,9 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
           (p.op.kind == MH_OP_ADAPTIVE_THRESHOLD))
         return fail(MH_UNSUPPORTED,"ShardedImage: the threshold operators are not sharded (AutoThresholdImage needs the "
           "bands' counts all-reduced, AdaptiveThresholdImage a halo)");
+      if ((p.op.kind == MH_OP_AUTO_LEVEL) || (p.op.kind == MH_OP_LINEAR_STRETCH) || (p.op.kind == MH_OP_NORMALIZE))
+        return fail(MH_UNSUPPORTED,"ShardedImage: AutoLevelImage, LinearStretchImage and NormalizeImage are not sharded "
+          "(the bands' range or counts would have to be all-reduced)");
       if (p.reach == (size_t) -1)
         return fail(MH_UNSUPPORTED,"ShardedImage: iterate-until-convergence has no halo bound");
       reach=p.reach > reach ? p.reach : reach;

@@ -368,8 +368,10 @@ MhStatus launch_histogram(const View &src,int intensity_mode,const MhImage *desc
   unsigned long long *hist_device);
 // shared_column >= 0: every channel selected by apply_mask maps through that one LUT column
 // device_mask (optional): a device word and-ed into apply_mask inside the kernel
+// single_column: lut_device is one column of 65536 entries that every selected channel maps through
 MhStatus launch_apply_lut(const View &img,const void *lut_device,uint32_t apply_mask,
-  const Roles &roles,int shared_column,const uint32_t *device_mask=nullptr);
+  const Roles &roles,int shared_column,const uint32_t *device_mask=nullptr,bool single_column=false,
+  const char *label="apply_lut");
 // histogram [65536][channels] -> Quantum-typed LUT + per-channel apply mask, on the device
 // cdf_device (optional, equalize): the running counts of channel cdf_column as 65536 uint32 (all of
 // them 0xffffffff when the frame has 2^32 pixels or more)
@@ -456,6 +458,29 @@ MhStatus launch_threshold_histogram(const View &img,const MhImage *desc,unsigned
 MhStatus adaptive_threshold_check(const View &src,size_t width,size_t height);
 MhStatus launch_adaptive_threshold(const View &src,const View &dst,size_t width,size_t height,double bias,
   uint32_t copy_mask);
+// The level operators (levels.hip), in place.  One sample of a channel of update_mask becomes:
+//   LEVEL              ClampPixel(ClampToQuantum(QuantumRange*(a*(q-b))))                a = scale, b = black
+//   LEVEL_POW          ... QuantumRange*gamma_pow(a*(q-b),c)                             c = PerceptibleReciprocal(gamma)
+//   LEVELIZE           ClampToQuantum((QuantumScale*q)*a+b)                              a = white-black, b = black
+//   LEVELIZE_POW       ClampToQuantum(gamma_pow(QuantumScale*q,c)*a+b)                   c = gamma
+//   SIGMOIDAL          ClampToQuantum(QuantumRange*((tanh(a*(QuantumScale*q-b))-c)/(d-c)))   a = 0.5*contrast,
+//                      b = QuantumScale*midpoint, c = Sigmoidal(0), d = Sigmoidal(1), both from the host's tanh
+//   SIGMOIDAL_INVERSE  ClampToQuantum(QuantumRange*(b+a*atanh(clamp((d-c)*(QuantumScale*q)+c))))   a = 2.0/contrast
+//   NEGATE             QuantumRange-q;  NEGATE_GRAY: only where IsPixelGray (colours: the colour channels)
+enum { MH_LEVELS_LEVEL=0,MH_LEVELS_LEVEL_POW=1,MH_LEVELS_LEVELIZE=2,MH_LEVELS_LEVELIZE_POW=3,MH_LEVELS_SIGMOIDAL=4,
+  MH_LEVELS_SIGMOIDAL_INVERSE=5,MH_LEVELS_NEGATE=6,MH_LEVELS_NEGATE_GRAY=7 };
+struct LevelsParams
+{
+  int mode=MH_LEVELS_LEVEL;
+  int colours=0;
+  uint32_t update_mask=0;
+  double a=0.0,b=0.0,c=0.0,d=0.0;
+};
+MhStatus launch_levels_point(const View &img,const LevelsParams &params);
+// GetImageRange's raw material: result_device[2c], [2c+1] = minimum and maximum of channel c (DBL_MAX and
+// -DBL_MAX for a channel the frame lacks), [2*MH_MAX_CHANNELS], [+1] = those of column 0 of channel 0, the
+// seed of every row.  column0_only: only the seed is scanned, the channels' slots are empty.
+MhStatus launch_levels_range(const View &img,bool column0_only,double *result_device);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

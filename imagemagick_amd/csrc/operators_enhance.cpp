@@ -11,6 +11,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <mutex>
 
 namespace mh {
 
@@ -179,6 +180,226 @@ MhStatus apply_histogram_lut(const View &view,const MhImage *image,const unsigne
   MH_TRY(launch_build_lut(view,hist,equalize,black_point,white_limit,
     lut.ptr,mask.as<uint32_t>(),colour_flag));
   return launch_apply_lut(view,lut.ptr,~0u,roles,shared_column,mask.as<uint32_t>());
+}
+
+// ------------------------------------------------------------------ the level operators
+// (MagickCore/enhance.c: LevelImage :2913, LevelizeImage :3062, GammaImage :2322, NegateImage :3940,
+// SigmoidalContrastImage :4267, LinearStretchImage :3347; MinMaxStretchImage histogram.c:927)
+static uint32_t update_mask_of(const MhImage *image)
+{
+  uint32_t update=0;
+  for (uint32_t c=0; c < image->number_channels; c++)
+    if ((image->channel_traits[c] & MH_TRAIT_UPDATE) != 0)
+      update|=1u<<c;
+  return update;
+}
+
+// ClampToQuantum of the Quantum type, widened to double
+static double clamp_to_quantum(double value,MhQuantumKind quantum)
+{
+  if (quantum != MH_QUANTUM_U16)
+    return (double) (float) value;
+  if (!(value > 0.0))
+    return 0.0;
+  if (value >= kQuantumRange)
+    return kQuantumRange;
+  return (double) (unsigned short) (value+0.5);
+}
+
+// gamma_pow, enhance.c:2317-2320
+static double gamma_pow(double value,double gamma)
+{
+  return value < 0.0 ? value : pow(value,gamma);
+}
+
+// A curve that calls libm, tabulated over the 65536 Q16 samples with the host's libm (the one the
+// reference links), Quantum-typed.  A few tables are kept per process, keyed by curve and
+// parameters: a batch with one parameter set builds its table once.
+enum { LEVELS_TABLE_LEVEL=0,LEVELS_TABLE_LEVELIZE=1,LEVELS_TABLE_SIGMOIDAL=2,LEVELS_TABLE_SIGMOIDAL_INVERSE=3,
+  LEVELS_TABLE_GAMMA=4 };
+struct LevelsTable
+{
+  int curve;
+  MhQuantumKind quantum;
+  double p[4];
+  std::shared_ptr<const std::vector<unsigned char>> column;
+};
+static std::mutex &levels_tables_lock() { static std::mutex &m=*new std::mutex; return m; }
+static std::vector<LevelsTable> &levels_tables() { static std::vector<LevelsTable> &v=*new std::vector<LevelsTable>; return v; }
+static unsigned long long levels_tables_built=0;
+
+static double levels_curve(int curve,const double *p,double q)
+{
+  switch (curve)
+  {
+    case LEVELS_TABLE_LEVEL:
+      return kQuantumRange*gamma_pow(p[0]*(q-p[1]),p[2]);
+    case LEVELS_TABLE_LEVELIZE:
+      return gamma_pow(kQuantumScale*q,p[2])*p[0]+p[1];
+    case LEVELS_TABLE_SIGMOIDAL:
+      return kQuantumRange*((tanh(p[0]*(kQuantumScale*q-p[1]))-p[2])/(p[3]-p[2]));
+    default:
+      break;
+  }
+  const double argument=(p[3]-p[2])*(kQuantumScale*q)+p[2];
+  const double clamped=argument < -1+kMagickEpsilon ? -1+kMagickEpsilon :
+    (argument > 1-kMagickEpsilon ? 1-kMagickEpsilon : argument);
+  return kQuantumRange*(p[1]+p[0]*atanh(clamped));
+}
+
+static std::shared_ptr<const std::vector<unsigned char>> levels_table(int curve,MhQuantumKind quantum,
+  const double *p)
+{
+  constexpr size_t kTables=16;
+  std::lock_guard<std::mutex> guard(levels_tables_lock());
+  std::vector<LevelsTable> &tables=levels_tables();
+  for (size_t i=0; i < tables.size(); i++)
+    if ((tables[i].curve == curve) && (tables[i].quantum == quantum) &&
+        (memcmp(tables[i].p,p,sizeof(tables[i].p)) == 0))
+      {
+        LevelsTable hit=std::move(tables[i]);
+        tables.erase(tables.begin()+(ptrdiff_t) i);
+        tables.insert(tables.begin(),std::move(hit));
+        return tables[0].column;
+      }
+  const size_t size=quantum == MH_QUANTUM_U16 ? sizeof(unsigned short) : sizeof(float);
+  auto column=std::make_shared<std::vector<unsigned char>>((size_t) MH_HISTOGRAM_BINS*size);
+  if (curve == LEVELS_TABLE_GAMMA)
+    {
+      std::vector<double> lut((size_t) MH_HISTOGRAM_BINS);
+      (void) MhGammaLUT(p[0],quantum,lut.data());
+      for (size_t i=0; i <= MH_MAXMAP; i++)
+        if (quantum == MH_QUANTUM_U16)
+          reinterpret_cast<unsigned short *>(column->data())[i]=(unsigned short) lut[i];
+        else
+          reinterpret_cast<float *>(column->data())[i]=(float) lut[i];
+    }
+  else
+    for (size_t i=0; i <= MH_MAXMAP; i++)
+      {
+        // LevelImage ends in ClampImage, which leaves a Q16 sample as it is
+        const double value=clamp_to_quantum(levels_curve(curve,p,(double) i),quantum);
+        if (quantum == MH_QUANTUM_U16)
+          reinterpret_cast<unsigned short *>(column->data())[i]=(unsigned short) value;
+        else
+          reinterpret_cast<float *>(column->data())[i]=(float) value;
+      }
+  levels_tables_built++;
+  LevelsTable entry;
+  entry.curve=curve;
+  entry.quantum=quantum;
+  memcpy(entry.p,p,sizeof(entry.p));
+  entry.column=column;
+  tables.insert(tables.begin(),std::move(entry));
+  if (tables.size() > kTables)
+    tables.pop_back();
+  return column;
+}
+
+// one tabulated curve applied to the channels of `update`
+static MhStatus apply_levels_table(const View &view,int curve,const double *p,uint32_t update,const char *label)
+{
+  if ((update == 0) || (view.columns == 0) || (view.rows == 0))
+    return MH_OK;
+  const std::shared_ptr<const std::vector<unsigned char>> column=levels_table(curve,view.quantum,p);
+  const void *device_column=nullptr;
+  std::shared_ptr<void> keep;
+  MH_TRY(shared_table(view.device,view.stream,column->data(),column->size(),&device_column,&keep));
+  Roles roles;
+  roles.update_mask=update;
+  return launch_apply_lut(view,device_column,update,roles,0,nullptr,true,label);
+}
+
+// LevelImage on an open frame, the channels of `update`
+static MhStatus level_view(const View &view,uint32_t update,double black_point,double white_point,double gamma)
+{
+  const double scale=perceptible_reciprocal(white_point-black_point);
+  const double exponent=perceptible_reciprocal(gamma);
+  if ((exponent != 1.0) && (view.quantum == MH_QUANTUM_U16))
+    {
+      const double p[4]={scale,black_point,exponent,0.0};
+      return apply_levels_table(view,LEVELS_TABLE_LEVEL,p,update,"levels_level_table");
+    }
+  LevelsParams params;
+  params.mode=exponent != 1.0 ? MH_LEVELS_LEVEL_POW : MH_LEVELS_LEVEL;    // pow(v,1.0) is v
+  params.update_mask=update;
+  params.a=scale;
+  params.b=black_point;
+  params.c=exponent;
+  return launch_levels_point(view,params);
+}
+
+// the ten words of launch_levels_range on the host
+static MhStatus range_to_host(const View &view,bool column0_only,double *slots)
+{
+  constexpr size_t bytes=2*(MH_MAX_CHANNELS+1)*sizeof(double);
+  Temp result;
+  MH_TRY(result.alloc(view.device,bytes,view.stream));
+  MH_TRY(launch_levels_range(view,column0_only,result.as<double>()));
+  MH_HIP(hipMemcpyAsync(slots,result.ptr,bytes,hipMemcpyDeviceToHost,view.stream));
+  MH_HIP(hipStreamSynchronize(view.stream));
+  return MH_OK;
+}
+
+// GetImageRange, statistic.c:1851-1929: every row starts from p[0], the offset-0 sample of its
+// first pixel, whatever the mask, so the range is over the channels of `update` and column 0 of
+// channel 0; *maxima starts at MagickMinimumValue and *minima at MagickMaximumValue
+static void combine_range(const double *slots,const View &view,uint32_t update,double *minimum,double *maximum)
+{
+  *maximum=2.22507385850720140E-308;
+  *minimum=1.79769313486231570E+308;
+  if ((view.columns == 0) || (view.rows == 0))
+    return;
+  for (int c=0; c <= MH_MAX_CHANNELS; c++)
+    {
+      if ((c < MH_MAX_CHANNELS) && (((update >> c) & 1u) == 0))
+        continue;
+      if (slots[2*c] < *minimum)
+        *minimum=slots[2*c];
+      if (slots[2*c+1] > *maximum)
+        *maximum=slots[2*c+1];
+    }
+}
+
+// MinMaxStretchImage on an open frame, histogram.c:927-975
+static MhStatus min_max_stretch_view(const View &view,const MhImage *image,double black,double white,double gamma)
+{
+  const uint32_t update=update_mask_of(image);
+  double slots[2*(MH_MAX_CHANNELS+1)],minimum,maximum;
+  MH_TRY(range_to_host(view,false,slots));
+  if (image->channel_mask == MH_ALL_CHANNELS)
+    {
+      combine_range(slots,view,update,&minimum,&maximum);
+      minimum+=black;
+      maximum-=white;
+      if (fabs(minimum-maximum) >= kMagickEpsilon)
+        MH_TRY(level_view(view,update,minimum,maximum,gamma));
+      return MH_OK;
+    }
+  // Per channel, in the order of the offsets.  The mask of offset i is the ChannelType bit 1 << i
+  // (histogram.c:966), which names the channel stored there unless that channel is alpha (bit 4):
+  // for the alpha offset no stored channel is selected, the range is the seed alone and nothing is
+  // levelled.  Levelling channel 0 changes column 0 of channel 0, the seed of the later ranges.
+  for (uint32_t i=0; i < image->number_channels; i++)
+    {
+      if (((update >> i) & 1u) == 0)
+        continue;
+      const uint32_t selected=(int32_t) i == image->alpha_offset ? 0u : 1u<<i;
+      combine_range(slots,view,selected,&minimum,&maximum);
+      minimum+=black;
+      maximum-=white;
+      if ((selected == 0) || !(fabs(minimum-maximum) >= kMagickEpsilon))
+        continue;
+      MH_TRY(level_view(view,selected,minimum,maximum,gamma));
+      if ((i == 0) && (image->number_channels > 1))
+        {
+          double seed[2*(MH_MAX_CHANNELS+1)];
+          MH_TRY(range_to_host(view,true,seed));
+          slots[2*MH_MAX_CHANNELS]=seed[2*MH_MAX_CHANNELS];
+          slots[2*MH_MAX_CHANNELS+1]=seed[2*MH_MAX_CHANNELS+1];
+        }
+    }
+  return MH_OK;
 }
 
 } // namespace mh
@@ -943,6 +1164,206 @@ MH_API MhStatus MagickHipRangeThresholdImage(MhImage *image,double low_black,dou
     kQuantumRange*perceptible_reciprocal(low_white-low_black),
     kQuantumRange*perceptible_reciprocal(high_black-high_white),image));
   return io.img.commit();
+}
+
+// ------------------------------------------------------------------ the level operators
+MH_API MhStatus MagickHipLevelImage(MhImage *image,double black_point,double white_point,double gamma)
+{
+  MH_TRY(check_image(image,"LevelImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(level_view(io.img.view,update_mask_of(image),black_point,white_point,gamma));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipLevelizeImage(MhImage *image,double black_point,double white_point,double gamma)
+{
+  MH_TRY(check_image(image,"LevelizeImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  const View &view=io.img.view;
+  const uint32_t update=update_mask_of(image);
+  if ((gamma != 1.0) && (view.quantum == MH_QUANTUM_U16))
+    {
+      const double p[4]={white_point-black_point,black_point,gamma,0.0};
+      MH_TRY(apply_levels_table(view,LEVELS_TABLE_LEVELIZE,p,update,"levels_levelize_table"));
+    }
+  else
+    {
+      LevelsParams params;
+      params.mode=gamma != 1.0 ? MH_LEVELS_LEVELIZE_POW : MH_LEVELS_LEVELIZE;     // pow(v,1.0) is v
+      params.update_mask=update;
+      params.a=white_point-black_point;
+      params.b=black_point;
+      params.c=gamma;
+      MH_TRY(launch_levels_point(view,params));
+    }
+  return io.img.commit();
+}
+
+// GammaImage's map, enhance.c:2354-2362
+MH_API MhStatus MhGammaLUT(double gamma,MhQuantumKind quantum,double *lut)
+{
+  if (lut == nullptr)
+    return fail(MH_BAD_ARGUMENT,"GammaLUT: null LUT");
+  memset(lut,0,(size_t) MH_HISTOGRAM_BINS*sizeof(double));
+  if (gamma != 0.0)
+    for (size_t i=0; i <= MH_MAXMAP; i++)
+      lut[i]=scale_map_to_quantum((double) MH_MAXMAP*pow((double) i/(double) MH_MAXMAP,perceptible_reciprocal(gamma)),
+        quantum);
+  return MH_OK;
+}
+
+MH_API MhStatus MagickHipGammaImage(MhImage *image,double gamma)
+{
+  MH_TRY(check_image(image,"GammaImage"));
+  if (gamma == 1.0)
+    return MH_OK;
+  InPlace io;
+  MH_TRY(io.open(image));
+  const double p[4]={gamma,0.0,0.0,0.0};
+  MH_TRY(apply_levels_table(io.img.view,LEVELS_TABLE_GAMMA,p,update_mask_of(image),"levels_gamma_table"));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipNegateImage(MhImage *image,int grayscale)
+{
+  MH_TRY(check_image(image,"NegateImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  LevelsParams params;
+  params.mode=grayscale != 0 ? MH_LEVELS_NEGATE_GRAY : MH_LEVELS_NEGATE;
+  params.update_mask=update_mask_of(image);
+  params.colours=(int) image->number_channels-(image->alpha_offset >= 0 ? 1 : 0);
+  MH_TRY(launch_levels_point(io.img.view,params));
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipSigmoidalContrastImage(MhImage *image,int sharpen,double contrast,double midpoint)
+{
+  MH_TRY(check_image(image,"SigmoidalContrastImage"));
+  if (contrast < kMagickEpsilon)
+    return MH_OK;
+  InPlace io;
+  MH_TRY(io.open(image));
+  const View &view=io.img.view;
+  const uint32_t update=update_mask_of(image);
+  // Sigmoidal(a,b,x) = tanh((0.5*a)*(x-b)), enhance.c:4207; the two constants of the call from the host's tanh
+  const double b=kQuantumScale*midpoint;
+  const double sig0=tanh((0.5*contrast)*(0.0-b)),sig1=tanh((0.5*contrast)*(1.0-b));
+  const double p[4]={sharpen != 0 ? 0.5*contrast : 2.0/contrast,b,sig0,sig1};
+  if (view.quantum == MH_QUANTUM_U16)
+    MH_TRY(apply_levels_table(view,sharpen != 0 ? LEVELS_TABLE_SIGMOIDAL : LEVELS_TABLE_SIGMOIDAL_INVERSE,p,update,
+      "levels_sigmoidal_table"));
+  else
+    {
+      LevelsParams params;
+      params.mode=sharpen != 0 ? MH_LEVELS_SIGMOIDAL : MH_LEVELS_SIGMOIDAL_INVERSE;
+      params.update_mask=update;
+      params.a=p[0];
+      params.b=p[1];
+      params.c=p[2];
+      params.d=p[3];
+      MH_TRY(launch_levels_point(view,params));
+    }
+  return io.img.commit();
+}
+
+MH_API MhStatus MagickHipImageRange(const MhImage *image,double *minimum,double *maximum)
+{
+  MH_TRY(check_image(image,"ImageRange"));
+  if ((minimum == nullptr) || (maximum == nullptr))
+    return fail(MH_BAD_ARGUMENT,"ImageRange: null result");
+  DeviceGuard guard;
+  Resident img;
+  const int device=resolve_device(image);
+  MH_TRY(img.open(image,0,image->memory == MH_MEMORY_DEVICE ? (hipStream_t) image->stream :
+    library_stream(device),device));
+  MH_HIP(guard.enter(img.view.device));
+  double slots[2*(MH_MAX_CHANNELS+1)];
+  MH_TRY(range_to_host(img.view,false,slots));
+  combine_range(slots,img.view,update_mask_of(image),minimum,maximum);
+  return MH_OK;
+}
+
+MH_API MhStatus MagickHipMinMaxStretchImage(MhImage *image,double black,double white,double gamma)
+{
+  MH_TRY(check_image(image,"MinMaxStretchImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  MH_TRY(min_max_stretch_view(io.img.view,image,black,white,gamma));
+  return io.img.commit();
+}
+
+// enhance.c:187-191
+MH_API MhStatus MagickHipAutoLevelImage(MhImage *image)
+{
+  return MagickHipMinMaxStretchImage(image,0.0,0.0,1.0);
+}
+
+MH_API MhStatus MagickHipLinearStretchImage(MhImage *image,double black_point,double white_point,size_t *black,
+  size_t *white)
+{
+  MH_TRY(check_image(image,"LinearStretchImage"));
+  InPlace io;
+  MH_TRY(io.open(image));
+  const View &view=io.img.view;
+  // enhance.c:3382-3401: counts of ScaleQuantumToMap(ClampToQuantum(intensity)); the intensity
+  // histogram gives every channel's column the same counts
+  std::vector<unsigned long long> counts;
+  MH_TRY(histogram_to_host(view,1,image,counts));
+  const size_t C=(size_t) view.channels;
+  // enhance.c:3406-3419
+  double intensity=0.0;
+  ptrdiff_t low,high;
+  for (low=0; low < (ptrdiff_t) MH_MAXMAP; low++)
+    {
+      intensity+=(double) counts[C*(size_t) low];
+      if (intensity >= black_point)
+        break;
+    }
+  intensity=0.0;
+  for (high=(ptrdiff_t) MH_MAXMAP; high != 0; high--)
+    {
+      intensity+=(double) counts[C*(size_t) high];
+      if (intensity >= white_point)
+        break;
+    }
+  if (black != nullptr)
+    *black=(size_t) low;
+  if (white != nullptr)
+    *white=(size_t) high;
+  MH_TRY(level_view(view,update_mask_of(image),scale_map_to_quantum((double) low,view.quantum),
+    scale_map_to_quantum((double) high,view.quantum),1.0));
+  return io.img.commit();
+}
+
+// enhance.c:4130-4140
+MH_API MhStatus MagickHipNormalizeImage(MhImage *image)
+{
+  if (image == nullptr)
+    return fail(MH_BAD_ARGUMENT,"NormalizeImage: null image");
+  const double black_point=0.02*(double) image->columns*(double) image->rows;
+  const double white_point=0.99*(double) image->columns*(double) image->rows;
+  return MagickHipContrastStretchImage(image,black_point,white_point,nullptr);
+}
+
+// enhance.c:224-252
+MH_API MhStatus MagickHipBrightnessContrastImage(MhImage *image,double brightness,double contrast)
+{
+  double slope=100.0*perceptible_reciprocal(100.0-contrast);
+  if (contrast < 0.0)
+    slope=0.01*contrast+1.0;
+  const double intercept=(0.01*brightness-0.5)*slope+0.5;
+  const double coefficients[2]={slope,intercept};
+  return MagickHipFunctionImage(image,MH_FUNCTION_POLYNOMIAL,2,coefficients);
+}
+
+// tables built since the process started (tests: a second call with the same parameters builds none)
+MH_API unsigned long long MhLevelsTablesBuilt(void)
+{
+  std::lock_guard<std::mutex> guard(levels_tables_lock());
+  return levels_tables_built;
 }
 
 } // extern "C"

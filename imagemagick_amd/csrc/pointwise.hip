@@ -2017,20 +2017,22 @@ MhStatus launch_equalize_cdf_apply(const View &img,const uint32_t *cdf,const voi
 }
 
 MhStatus launch_apply_lut(const View &img,const void *lut,uint32_t apply_mask,const Roles &roles,
-  int shared_column,const uint32_t *device_mask)
+  int shared_column,const uint32_t *device_mask,bool single_column,const char *label)
 {
   uint32_t mask=apply_mask & roles.update_mask;
+  if (single_column)
+    shared_column=0;
   if ((shared_column >= 0) && (img.quantum == MH_QUANTUM_U16) &&
       (img.columns*img.rows >= ((size_t) 1 << 20)))
     switch (img.channels)
     {
-      case 1: return apply_lut_shared<1>(img,lut,shared_column,mask,device_mask);
-      case 2: return apply_lut_shared<2>(img,lut,shared_column,mask,device_mask);
-      case 3: return apply_lut_shared<3>(img,lut,shared_column,mask,device_mask);
-      default: return apply_lut_shared<4>(img,lut,shared_column,mask,device_mask);
+      case 1: return apply_lut_shared<1>(img,lut,shared_column,mask,device_mask,single_column,label);
+      case 2: return apply_lut_shared<2>(img,lut,shared_column,mask,device_mask,single_column,label);
+      case 3: return apply_lut_shared<3>(img,lut,shared_column,mask,device_mask,single_column,label);
+      default: return apply_lut_shared<4>(img,lut,shared_column,mask,device_mask,single_column,label);
     }
   return dispatch_layout(img.quantum,img.channels,[&](auto L) {
-    return apply_lut_typed<typename decltype(L)::Q,L.C>(img,lut,mask,device_mask); });
+    return apply_lut_typed<typename decltype(L)::Q,L.C>(img,lut,mask,device_mask,single_column,label); });
 }
 
 

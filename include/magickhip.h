@@ -748,6 +748,75 @@ MH_API MhStatus MagickHipModulateImage(MhImage *image,double percent_brightness,
 MH_API MhStatus MagickHipFunctionImage(MhImage *image,MhFunction function,
   size_t number_parameters,const double *parameters);
 
+/* ---- The level operators, MagickCore/enhance.c and histogram.c (no accelerate hook in the
+   reference).  All in place, 1-4 channels, host and device memory, both Quantum
+   types.  Only channels whose trait carries MH_TRAIT_UPDATE are written.  fp64 in the
+   reference's operation order.  Q16 results are bit-identical to the reference in both precision
+   modes: a curve that calls libm (gamma != 1, the sigmoidals) is tabulated over the 65536 samples
+   on the host, with the host's libm, and applied as a table; a few tables are kept per process.
+   Float Quantum is evaluated on the device: bit-identical where no libm is involved (gamma == 1,
+   NegateImage) and for GammaImage (table-driven in the reference too), within one float ULP where
+   the device's pow / tanh / atanh is.  There is no FAST variant.  NaN and infinite samples are
+   outside the contract. */
+
+/* LevelImage(image,black_point,white_point,gamma), enhance.c:2913-3018:
+   ClampToQuantum(QuantumRange*gamma_pow(PerceptibleReciprocal(white-black)*(q-black),
+   PerceptibleReciprocal(gamma))), gamma_pow(v,g) = v < 0 ? v : pow(v,g); then ClampImage: a float
+   result below 0 becomes 0, one at or above QuantumRange becomes QuantumRange. */
+MH_API MhStatus MagickHipLevelImage(MhImage *image,double black_point,double white_point,double gamma);
+
+/* LevelizeImage, enhance.c:3062-3170: ClampToQuantum(gamma_pow(QuantumScale*q,gamma)*(white-black)+
+   black); no ClampImage: float results may leave the range. */
+MH_API MhStatus MagickHipLevelizeImage(MhImage *image,double black_point,double white_point,double gamma);
+
+/* GammaImage, enhance.c:2322-2440: gamma == 1 leaves the frame untouched; otherwise
+   map[ScaleQuantumToMap(ClampToQuantum(q))] with the map of MhGammaLUT, on both Quantum types.
+   image->gamma *= gamma is the caller's side effect. */
+MH_API MhStatus MagickHipGammaImage(MhImage *image,double gamma);
+
+/* NegateImage(image,grayscale), enhance.c:3940-4100: QuantumRange-q; with grayscale != 0 only in
+   pixels whose |R-G| and |G-B| are below MagickEpsilon (IsPixelGray: every pixel of a frame with
+   fewer than three colour channels). */
+MH_API MhStatus MagickHipNegateImage(MhImage *image,int grayscale);
+
+/* SigmoidalContrastImage(image,sharpen,contrast,midpoint), enhance.c:4267-4407, the tanh / atanh
+   form; midpoint in Quantum units.  contrast < MagickEpsilon leaves the frame untouched. */
+MH_API MhStatus MagickHipSigmoidalContrastImage(MhImage *image,int sharpen,double contrast,double midpoint);
+
+/* GetImageRange, statistic.c:1851-1929, with its seed: every row starts from the offset-0 sample
+   of its first pixel whatever the mask, so the range is over the samples of the Update channels
+   AND column 0 of channel 0; *maximum starts at MagickMinimumValue (2.2e-308), *minimum at
+   MagickMaximumValue. */
+MH_API MhStatus MagickHipImageRange(const MhImage *image,double *minimum,double *maximum);
+
+/* MinMaxStretchImage(image,black,white,gamma), histogram.c:927-975.  channel_mask ==
+   MH_ALL_CHANNELS: one range over the Update channels, min += black, max -= white, LevelImage
+   unless |min-max| < MagickEpsilon.  Any other mask: for every offset whose trait carries Update,
+   in order, the range and the LevelImage of that channel alone; the reference selects it with the
+   ChannelType bit 1 << offset, which names no stored channel at the alpha offset: alpha is never
+   levelled in this mode.  Channel 0 is levelled before the later channels are measured, and its
+   column 0 is part of their range.  AutoLevelImage (enhance.c:187) is (0,0,1). */
+MH_API MhStatus MagickHipMinMaxStretchImage(MhImage *image,double black,double white,double gamma);
+MH_API MhStatus MagickHipAutoLevelImage(MhImage *image);
+
+/* LinearStretchImage(image,black_point,white_point), enhance.c:3347-3427; the points are pixel
+   counts.  65536 counts of ScaleQuantumToMap(ClampToQuantum(intensity)) on the device, the scan on
+   the host, then LevelImage(ScaleMapToQuantum(black),ScaleMapToQuantum(white),1).  *black and
+   *white (optional) receive the two bins: the reference's "histogram:linear-stretch" property is
+   "%gx%g%%" of 100.0*black/MaxMap and 100.0*white/MaxMap. */
+MH_API MhStatus MagickHipLinearStretchImage(MhImage *image,double black_point,double white_point,
+  size_t *black,size_t *white);
+
+/* NormalizeImage, enhance.c:4130-4140: ContrastStretchImage at 0.02 and 0.99 of the pixel count
+   (MagickHipContrastStretchImage: MH_UNSUPPORTED for a colour frame whose pixels are all gray). */
+MH_API MhStatus MagickHipNormalizeImage(MhImage *image);
+
+/* BrightnessContrastImage, enhance.c:224-252: FunctionImage(Polynomial) with slope and intercept. */
+MH_API MhStatus MagickHipBrightnessContrastImage(MhImage *image,double brightness,double contrast);
+
+/* Tone-curve tables built by this process so far (a call whose parameters hit the cache builds none). */
+MH_API unsigned long long MhLevelsTablesBuilt(void);
+
 /* ---------------------------------------------------------- building blocks */
 /* Exposed so a row-sharded image (one band per GPU / per process) can run the
    global-histogram operators with one all-reduce between the phases
@@ -770,6 +839,10 @@ MH_API MhStatus MhContrastStretchLUT(const uint64_t *histogram,uint32_t number_c
   MhQuantumKind quantum,double *lut,uint32_t *apply_mask);
 MH_API MhStatus MhEqualizeLUT(const uint64_t *histogram,uint32_t number_channels,
   MhQuantumKind quantum,double *lut,uint32_t *apply_mask);
+
+/* GammaImage's map, enhance.c:2354-2362: lut[i] = ScaleMapToQuantum(MaxMap*pow(i/MaxMap,
+   PerceptibleReciprocal(gamma))) for the 65536 bins, all zero when gamma == 0; one column. */
+MH_API MhStatus MhGammaLUT(double gamma,MhQuantumKind quantum,double *lut);
 
 /* q[c] = ClampToQuantum(lut[ScaleQuantumToMap(q[c])*number_channels + c]) for
    Update channels selected by apply_mask (enhance.c:1778-1788, :2252-2262).
@@ -841,9 +914,19 @@ typedef enum
                                   tile grid belongs to the whole frame, not to a row band */
   MH_OP_THRESHOLD = 14,        /* args: threshold (BilevelImage) */
   MH_OP_AUTO_THRESHOLD = 15,   /* args: MhAutoThresholdMethod */
-  MH_OP_ADAPTIVE_THRESHOLD = 16 /* args: width, height, bias.  These three: MagickHipBatchImages only;
+  MH_OP_ADAPTIVE_THRESHOLD = 16, /* args: width, height, bias.  These three: MagickHipBatchImages only;
                                   MagickHipShardedImage returns MH_UNSUPPORTED (AutoThresholdImage would
                                   need the bands' counts all-reduced, AdaptiveThresholdImage a halo) */
+  MH_OP_LEVEL = 17,            /* args: black_point, white_point, gamma */
+  MH_OP_LEVELIZE = 18,         /* args: black_point, white_point, gamma */
+  MH_OP_GAMMA = 19,            /* args: gamma */
+  MH_OP_NEGATE = 20,           /* args: grayscale */
+  MH_OP_SIGMOIDAL_CONTRAST = 21, /* args: sharpen, contrast, midpoint.  These five are pointwise:
+                                  MagickHipShardedImage runs them band by band, no halo, no collective */
+  MH_OP_AUTO_LEVEL = 22,
+  MH_OP_LINEAR_STRETCH = 23,   /* args: black_point, white_point (pixel counts) */
+  MH_OP_NORMALIZE = 24         /* These three: MagickHipBatchImages only; MagickHipShardedImage returns
+                                  MH_UNSUPPORTED (the bands' range or counts would have to be all-reduced) */
 } MhOperatorKind;
 
 typedef struct MhOperator

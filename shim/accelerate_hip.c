@@ -1155,6 +1155,152 @@ MagickPrivate MagickBooleanType AccelerateAutoThresholdImage(Image *image,
   return(RetagThresholdedImage(call.library,image,exception));
 }
 
+/*
+  The level operators' call sites (the shim's own hooks, shim/patch_hooks.py): the top of LevelImage
+  (enhance.c:2938), LevelizeImage (:3092), GammaImage (:2354), NegateImage (:3964),
+  SigmoidalContrastImage (:4306), LinearStretchImage (:3375) and MinMaxStretchImage
+  (histogram.c:941).  They are pointwise on the samples of the Update channels, in any colourspace;
+  what the library cannot see is gated here (IsLayoutAcceleratable: a PseudoClass image has a
+  colormap to level too, a masked image pixels to leave alone).  A declined call has touched
+  nothing.  NormalizeImage and BrightnessContrastImage need no hook of their own: they reach the
+  ContrastStretchImage and FunctionImage ones.
+*/
+#define BeginLevelsCall(call,image,exception) \
+  ((IsLayoutAcceleratable(image) != MagickFalse) && \
+   (BeginHipCall((call),(image),0,0,(exception)) != MagickFalse))
+
+static MagickBooleanType EndLevelsCall(HipCall *call,const Image *image,const MhStatus status)
+{
+  (void) EndHipCall(call,status);
+  if (status != MH_OK)
+    return(MagickFalse);
+  MarkDeviceCopyNewer(image);
+  return(MagickTrue);
+}
+
+MagickPrivate MagickBooleanType AccelerateLevelImage(Image *image,const double black_point,
+  const double white_point,const double gamma,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->LevelImage(&call.source,black_point,white_point,
+        gamma)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  return(MagickTrue);
+}
+
+MagickPrivate MagickBooleanType AccelerateLevelizeImage(Image *image,const double black_point,
+  const double white_point,const double gamma,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->LevelizeImage(&call.source,black_point,white_point,
+        gamma)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  return(MagickTrue);
+}
+
+/* behind GammaImage's `gamma == 1.0` return; image->gamma as enhance.c:2442-2443 leaves it */
+MagickPrivate MagickBooleanType AccelerateGammaImage(Image *image,const double gamma,
+  ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->GammaImage(&call.source,gamma)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  if (image->gamma != 0.0)
+    image->gamma*=gamma;
+  return(MagickTrue);
+}
+
+MagickPrivate MagickBooleanType AccelerateNegateImage(Image *image,
+  const MagickBooleanType grayscale,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->NegateImage(&call.source,
+        grayscale != MagickFalse ? 1 : 0)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  return(MagickTrue);
+}
+
+/* behind SigmoidalContrastImage's `contrast < MagickEpsilon` return */
+MagickPrivate MagickBooleanType AccelerateSigmoidalContrastImage(Image *image,
+  const MagickBooleanType sharpen,const double contrast,const double midpoint,
+  ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->SigmoidalContrastImage(&call.source,
+        sharpen != MagickFalse ? 1 : 0,contrast,midpoint)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  return(MagickTrue);
+}
+
+/* the range scans, the per-channel order and the LevelImage calls all run in the library */
+MagickPrivate MagickBooleanType AccelerateMinMaxStretchImage(Image *image,const double black,
+  const double white,const double gamma,ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  if (EndLevelsCall(&call,image,call.library->MinMaxStretchImage(&call.source,black,white,
+        gamma)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  return(MagickTrue);
+}
+
+MagickPrivate MagickBooleanType AccelerateLinearStretchImage(Image *image,
+  const double black_point,const double white_point,ExceptionInfo *exception)
+{
+  char
+    property[MagickPathExtent];
+
+  HipCall
+    call;
+
+  size_t
+    black,
+    white;
+
+  if (BeginLevelsCall(&call,image,exception) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  black=0;
+  white=0;
+  if (EndLevelsCall(&call,image,call.library->LinearStretchImage(&call.source,black_point,
+        white_point,&black,&white)) == MagickFalse)
+    return(HipDeclined(image,MagickFalse));
+  HipAccepted(image);
+  /* enhance.c:3423-3425 */
+  (void) FormatLocaleString(property,MagickPathExtent,"%gx%g%%",100.0*(ssize_t) black/MaxMap,
+    100.0*(ssize_t) white/MaxMap);
+  (void) SetImageProperty(image,"histogram:linear-stretch",property,exception);
+  return(MagickTrue);
+}
+
 /* DespeckleImage's call site: effect.c:1342-1346 */
 MagickPrivate Image *AccelerateDespeckleImage(const Image *image,ExceptionInfo *exception)
 {

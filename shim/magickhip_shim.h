@@ -53,6 +53,13 @@ typedef struct _HipLibrary
   MhStatus (*BilevelImage)(MhImage *,double);
   MhStatus (*AutoThresholdImage)(MhImage *,MhAutoThresholdMethod,double *);
   MhStatus (*AdaptiveThresholdImage)(const MhImage *,MhImage *,size_t,size_t,double);
+  MhStatus (*LevelImage)(MhImage *,double,double,double);
+  MhStatus (*LevelizeImage)(MhImage *,double,double,double);
+  MhStatus (*GammaImage)(MhImage *,double);
+  MhStatus (*NegateImage)(MhImage *,int);
+  MhStatus (*SigmoidalContrastImage)(MhImage *,int,double,double);
+  MhStatus (*MinMaxStretchImage)(MhImage *,double,double,double);
+  MhStatus (*LinearStretchImage)(MhImage *,double,double,size_t *,size_t *);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

@@ -182,6 +182,13 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(BilevelImage,"MagickHipBilevelImage");
   MH_RESOLVE(AutoThresholdImage,"MagickHipAutoThresholdImage");
   MH_RESOLVE(AdaptiveThresholdImage,"MagickHipAdaptiveThresholdImage");
+  MH_RESOLVE(LevelImage,"MagickHipLevelImage");
+  MH_RESOLVE(LevelizeImage,"MagickHipLevelizeImage");
+  MH_RESOLVE(GammaImage,"MagickHipGammaImage");
+  MH_RESOLVE(NegateImage,"MagickHipNegateImage");
+  MH_RESOLVE(SigmoidalContrastImage,"MagickHipSigmoidalContrastImage");
+  MH_RESOLVE(MinMaxStretchImage,"MagickHipMinMaxStretchImage");
+  MH_RESOLVE(LinearStretchImage,"MagickHipLinearStretchImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Generates, at build time, copies of seven MagickCore sources with the accelerate call
+"""Generates, at build time, copies of eight MagickCore sources with the accelerate call
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
-StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage, CLAHEImage, AdaptiveThresholdImage, BilevelImage
-and AutoThresholdImage lack altogether.  Each hook is the reference's own three-line idiom
+StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage, CLAHEImage, AdaptiveThresholdImage, BilevelImage,
+AutoThresholdImage, LevelImage, LevelizeImage, GammaImage, NegateImage, SigmoidalContrastImage, LinearStretchImage and
+MinMaxStretchImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -55,6 +56,23 @@ ENHANCE_PROTOTYPE = '''
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 extern MagickPrivate MagickBooleanType AccelerateCLAHEImage(Image *,const size_t,const size_t,
   const size_t,const double,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateLevelImage(Image *,const double,const double,const double,
+  ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateLevelizeImage(Image *,const double,const double,const double,
+  ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateGammaImage(Image *,const double,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateNegateImage(Image *,const MagickBooleanType,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateSigmoidalContrastImage(Image *,const MagickBooleanType,
+  const double,const double,ExceptionInfo *);
+extern MagickPrivate MagickBooleanType AccelerateLinearStretchImage(Image *,const double,const double,
+  ExceptionInfo *);
+#endif
+'''
+
+HISTOGRAM_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate MagickBooleanType AccelerateMinMaxStretchImage(Image *,const double,const double,
+  const double,ExceptionInfo *);
 #endif
 '''
 
@@ -155,11 +173,30 @@ def enhance(text):
     # geometry, so that both colourspace transforms and the equalisation run on the device
     text = after_includes(text, ENHANCE_PROTOTYPE)
     anchor = "  range_info.min=0;\n"
-    return in_function(text, "MagickExport MagickBooleanType CLAHEImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+    text = in_function(text, "MagickExport MagickBooleanType CLAHEImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
   if (AccelerateCLAHEImage(image,width,height,number_bins,clip_limit,exception) != MagickFalse)
     return(MagickTrue);
 #endif
 ''' + anchor, "enhance.c")
+    # The level operators have none either: one at the top of each, in front of the first statement
+    # behind the asserts (GammaImage and SigmoidalContrastImage: behind their "nothing to do" return)
+    colormap = "  if (image->storage_class == PseudoClass)\n"
+    for function, anchor, call in (
+            ("LevelImage(", colormap, "AccelerateLevelImage(image,black_point,white_point,gamma,exception)"),
+            ("LevelizeImage(", colormap, "AccelerateLevelizeImage(image,black_point,white_point,gamma,exception)"),
+            ("GammaImage(", "  gamma_map=(Quantum *) AcquireQuantumMemory(MaxMap+1UL,sizeof(*gamma_map));\n",
+             "AccelerateGammaImage(image,gamma,exception)"),
+            ("NegateImage(", colormap, "AccelerateNegateImage(image,grayscale,exception)"),
+            ("SigmoidalContrastImage(", colormap,
+             "AccelerateSigmoidalContrastImage(image,sharpen,contrast,midpoint,exception)"),
+            ("LinearStretchImage(", "  histogram=(double *) AcquireQuantumMemory(MaxMap+1UL,sizeof(*histogram));\n",
+             "AccelerateLinearStretchImage(image,black_point,white_point,exception)")):
+        text = in_function(text, "MagickExport MagickBooleanType " + function, anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  if (%s != MagickFalse)
+    return(MagickTrue);
+#endif
+''' % call + anchor, "enhance.c")
+    return text
 
 
 def colorspace(text):
@@ -222,12 +259,23 @@ def threshold(text):
 ''' + anchor, "threshold.c")
 
 
+def histogram(text):
+    # MinMaxStretchImage (AutoLevelImage's body) has no accelerate hook in the reference: one at its top
+    text = after_includes(text, HISTOGRAM_PROTOTYPE)
+    anchor = "  status=MagickTrue;\n"
+    return in_function(text, "MagickExport MagickBooleanType MinMaxStretchImage(", anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  if (AccelerateMinMaxStretchImage(image,black,white,gamma,exception) != MagickFalse)
+    return(MagickTrue);
+#endif
+''' + anchor, "histogram.c")
+
+
 def main():
     source, out = sys.argv[1], sys.argv[2]
     os.makedirs(out, exist_ok=True)
     for name, fn in (("morphology.c", morphology), ("effect.c", effect), ("enhance.c", enhance),
                      ("colorspace.c", colorspace), ("visual-effects.c", visual_effects),
-                     ("statistic.c", statistic), ("threshold.c", threshold)):
+                     ("statistic.c", statistic), ("threshold.c", threshold), ("histogram.c", histogram)):
         text = open(os.path.join(source, name), encoding="latin-1").read()
         patched = fn(text)
         with open(os.path.join(out, name), "w", encoding="latin-1") as f:
