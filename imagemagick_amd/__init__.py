@@ -19,7 +19,8 @@ from ._lib import (MagickHipError, MhImage, COLORSPACES, MORPHOLOGY, FILTERS,  #
                    ALL_CHANNELS, SYNC_CHANNELS)
 
 __all__ = ["Image", "blur_image", "convolve_image", "morphology_image", "morphology_primitive",
-           "unsharp_mask_image", "resize_image", "contrast_stretch_image", "equalize_image", "clahe_image",
+           "unsharp_mask_image", "resize_image", "sample_image", "scale_image", "thumbnail_image",
+           "scale_image_plan", "sample_image_offsets", "contrast_stretch_image", "equalize_image", "clahe_image",
            "bilevel_image", "auto_threshold_image", "adaptive_threshold_image", "black_threshold_image",
            "white_threshold_image", "range_threshold_image", "auto_threshold_from_histogram",
            "level_image", "levelize_image", "gamma_image", "negate_image", "sigmoidal_contrast_image",
@@ -484,6 +485,66 @@ def resize_image(image, columns, rows, filter="lanczos"):
     return out
 
 
+def sample_image(image, columns, rows, offset=None):
+    """SampleImage(image, columns, rows) — MagickCore/resize.c:3907.  offset: the sample:offset artifact
+    in percent, one number or (x, y); None = the default (the mid-point of each sample region)."""
+    lib = _lib.load()
+    if offset is None:
+        offset = (-1.0, -1.0)
+    elif not isinstance(offset, (tuple, list)):
+        offset = (offset, offset)
+    out = image.like(rows=rows, columns=columns)
+    _lib.check(lib.MagickHipSampleImage(ctypes.byref(image.descriptor()), ctypes.byref(out.descriptor()),
+                                        float(offset[0]), float(offset[1])))
+    return out
+
+
+def scale_image(image, columns, rows):
+    """ScaleImage(image, columns, rows) — MagickCore/resize.c:4106."""
+    lib = _lib.load()
+    out = image.like(rows=rows, columns=columns)
+    _lib.check(lib.MagickHipScaleImage(ctypes.byref(image.descriptor()), ctypes.byref(out.descriptor())))
+    return out
+
+
+def thumbnail_image(image, columns, rows, filter="undefined"):
+    """The pixels of ThumbnailImage(image, columns, rows) — MagickCore/resize.c:4591; filter:
+    image->filter, "undefined" = LanczosSharp."""
+    lib = _lib.load()
+    out = image.like(rows=rows, columns=columns)
+    _lib.check(lib.MagickHipThumbnailImage(ctypes.byref(image.descriptor()), ctypes.byref(out.descriptor()),
+                                           FILTERS[filter.lower()]))
+    return out
+
+
+def scale_image_plan(source, destination, axis):
+    """MhScaleImagePlan: ScaleImage's host plan for one axis (0 = rows, 1 = columns) as (counts, indices,
+    weights); None when the reference's walk cannot be realised."""
+    lib = _lib.load()
+    counts = np.zeros(destination, dtype=np.uint32)
+    capacity = 2 * (source + destination) + 4
+    indices = np.zeros(capacity, dtype=np.int32)
+    weights = np.zeros(capacity, dtype=np.float64)
+    total = lib.MhScaleImagePlan(source, destination, axis, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
+                                 indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                 weights.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), capacity)
+    if total == -2:
+        return None
+    if total < 0 or total > capacity:
+        raise MagickHipError(3, "MhScaleImagePlan(%d, %d, %d) returned %d" % (source, destination, axis, total))
+    return counts, indices[:total].copy(), weights[:total].copy()
+
+
+def sample_image_offsets(source, destination, offset_percent=-1.0):
+    """MhSampleImageOffsets: SampleImage's offset table for one axis; None when it leaves the frame."""
+    lib = _lib.load()
+    offsets = np.zeros(destination, dtype=np.int64)
+    if lib.MhSampleImageOffsets(source, destination, float(offset_percent),
+                                offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))) != 0:
+        return None
+    return offsets
+
+
 def contrast_stretch_image(image, black_point, white_point):
     """ContrastStretchImage(image, black, white), in place — MagickCore/enhance.c:1544."""
     lib = _lib.load()
@@ -853,7 +914,8 @@ def _operators(chain):
     ("autothreshold", "OTSU"), ("adaptivethreshold", width, height, bias), ("level", black, white, gamma),
     ("levelize", black, white, gamma), ("gamma", gamma), ("negate", grayscale), ("sigmoidalcontrast",
     sharpen, contrast, midpoint), ("autolevel",), ("linearstretch", black_point, white_point),
-    ("normalize",)] -> an MhOperator array (and the byte strings it points at)."""
+    ("normalize",), ("sample", columns, rows), ("scale", columns, rows), ("thumbnail", columns, rows,
+    "LanczosSharp")] -> an MhOperator array (and the byte strings it points at)."""
     ops = (_lib.MhOperator * len(chain))()
     keep = []
     for i, step in enumerate(chain):
@@ -869,6 +931,8 @@ def _operators(chain):
             args = [MORPHOLOGY[args[0].lower()], args[1]]
         elif name == "resize":
             args = [args[0], args[1], FILTERS[args[2].lower()] if len(args) > 2 else FILTERS["lanczos"]]
+        elif name == "thumbnail":
+            args = [args[0], args[1], FILTERS[args[2].lower()] if len(args) > 2 else FILTERS["undefined"]]
         elif name == "statistic":
             args = [_lib.STATISTICS[args[0].lower()] if isinstance(args[0], str) else args[0], args[1], args[2]]
         elif name == "autothreshold":

@@ -124,7 +124,8 @@ OPERATORS = {"blur": 1, "gaussianblur": 2, "unsharpmask": 3, "resize": 4, "morph
              "bilateralblur": 10, "selectiveblur": 11, "kuwahara": 12, "clahe": 13,
              "threshold": 14, "autothreshold": 15, "adaptivethreshold": 16,
              "level": 17, "levelize": 18, "gamma": 19, "negate": 20, "sigmoidalcontrast": 21,
-             "autolevel": 22, "linearstretch": 23, "normalize": 24}
+             "autolevel": 22, "linearstretch": 23, "normalize": 24,
+             "sample": 25, "scale": 26, "thumbnail": 27}
 
 # AutoThresholdMethod, MagickCore/threshold.h:25-31 (lower-case keys) -> MhAutoThresholdMethod
 AUTO_THRESHOLD = {"undefined": 0, "kapur": 1, "otsu": 2, "triangle": 3}
@@ -234,6 +235,13 @@ PROTOTYPES = [
     ("MagickHipResizeImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_int]),
     ("MagickHipResizeImageWithFilter", ctypes.c_int, [_P(MhImage), _P(MhImage),
                                                       ctypes.c_void_p]),
+    ("MagickHipSampleImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_double, ctypes.c_double]),
+    ("MagickHipScaleImage", ctypes.c_int, [_P(MhImage), _P(MhImage)]),
+    ("MagickHipThumbnailImage", ctypes.c_int, [_P(MhImage), _P(MhImage), ctypes.c_int]),
+    ("MhScaleImagePlan", ctypes.c_longlong, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _P(ctypes.c_uint),
+                                             _P(ctypes.c_int), _P(ctypes.c_double), ctypes.c_size_t]),
+    ("MhSampleImageOffsets", ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double,
+                                            _P(ctypes.c_longlong)]),
     ("MagickHipContrastStretchImage", ctypes.c_int, [_P(MhImage), ctypes.c_double,
                                                      ctypes.c_double, _P(ctypes.c_int)]),
     ("MagickHipEqualizeImage", ctypes.c_int, [_P(MhImage)]),

@@ -185,7 +185,7 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
             p.stencil=true;
             break;
           }
-        case MH_OP_RESIZE: case MH_OP_COLORSPACE:
+        case MH_OP_RESIZE: case MH_OP_COLORSPACE: case MH_OP_SAMPLE: case MH_OP_SCALE: case MH_OP_THUMBNAIL:
           break;
         case MH_OP_CLAHE:
           // width, height, number_bins are size_t arguments of the call
@@ -229,6 +229,12 @@ struct Working
   }
 };
 
+// the operators whose result has the geometry of args[0] x args[1]
+static bool changes_geometry(uint32_t kind)
+{
+  return (kind == MH_OP_RESIZE) || (kind == MH_OP_SAMPLE) || (kind == MH_OP_SCALE) || (kind == MH_OP_THUMBNAIL);
+}
+
 // One operator on `cur`.  New-image operators allocate their result from the pool and release
 // their input; in-place operators mutate cur.  Everything is enqueued on cur.stream.
 static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
@@ -268,12 +274,12 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       break;
   }
   MhImage next=cur.image;
-  if (op.kind == MH_OP_RESIZE)
+  if (changes_geometry(op.kind))
     {
+      if (!(op.args[0] >= 1.0) || !(op.args[1] >= 1.0) || (op.args[0] > 4294967295.0) || (op.args[1] > 4294967295.0))
+        return fail(MH_BAD_ARGUMENT,"operator %u: a result of %gx%g",op.kind,op.args[0],op.args[1]);
       next.columns=(size_t) op.args[0];
       next.rows=(size_t) op.args[1];
-      if ((next.columns == 0) || (next.rows == 0))
-        return fail(MH_BAD_ARGUMENT,"resize to %zux%zu",next.columns,next.rows);
     }
   void *memory=nullptr;
   MH_TRY(pool_alloc(cur.device,image_bytes(next),cur.stream,&memory));
@@ -292,6 +298,15 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
       break;
     case MH_OP_RESIZE:
       status=MagickHipResizeImage(&cur.image,&next,(MhFilterType) (int) op.args[2]);
+      break;
+    case MH_OP_SAMPLE:
+      status=MagickHipSampleImage(&cur.image,&next,-1.0,-1.0);
+      break;
+    case MH_OP_SCALE:
+      status=MagickHipScaleImage(&cur.image,&next);
+      break;
+    case MH_OP_THUMBNAIL:
+      status=MagickHipThumbnailImage(&cur.image,&next,(MhFilterType) (int) op.args[2]);
       break;
     case MH_OP_STATISTIC:
       status=MagickHipStatisticImage(&cur.image,&next,(MhStatisticType) (int) op.args[0],(size_t) op.args[1],
@@ -732,7 +747,7 @@ MH_API MhStatus MagickHipBatchImages(const MhOperator *operators,size_t number_o
   MH_TRY(prepare(operators,number_operators,chain));
   if (results == nullptr)
     for (const PreparedOperator &p : chain)
-      if (p.op.kind == MH_OP_RESIZE)
+      if (changes_geometry(p.op.kind))
         return fail(MH_BAD_ARGUMENT,"BatchImages: a chain that resizes needs result descriptors");
   for (size_t i=0; i < number_images; i++)
     {
@@ -889,8 +904,8 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
   size_t reach=0;
   for (const PreparedOperator &p : chain)
     {
-      if (p.op.kind == MH_OP_RESIZE)
-        return fail(MH_UNSUPPORTED,"ShardedImage: resize changes the geometry");
+      if (changes_geometry(p.op.kind))
+        return fail(MH_UNSUPPORTED,"ShardedImage: resize, sample, scale and thumbnail change the geometry");
       if (p.op.kind == MH_OP_CLAHE)
         return fail(MH_UNSUPPORTED,"ShardedImage: CLAHEImage's tile grid belongs to the whole frame");
       if ((p.op.kind == MH_OP_THRESHOLD) || (p.op.kind == MH_OP_AUTO_THRESHOLD) ||

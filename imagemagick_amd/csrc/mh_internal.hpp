@@ -481,6 +481,15 @@ MhStatus launch_levels_point(const View &img,const LevelsParams &params);
 // -DBL_MAX for a channel the frame lacks), [2*MH_MAX_CHANNELS], [+1] = those of column 0 of channel 0, the
 // seed of every row.  column0_only: only the seed is scanned, the channels' slots are empty.
 MhStatus launch_levels_range(const View &img,bool column0_only,double *result_device);
+// SampleImage and ScaleImage (scale.hip).  blend_mask: channels weighted by alpha (Blend trait under an
+// active alpha), store_mask: channels with a defined trait on both sides; the others keep the
+// destination's bits (the kernels read the destination pixel then, so the caller brings a host destination
+// to the device first).  alpha: the alpha offset, -1 when image->alpha_trait is undefined.
+struct ScalePlan;
+MhStatus launch_sample(const View &src,const View &dst,const long long *x_offset,const long long *y_offset,
+  uint32_t store_mask);
+MhStatus launch_scale(const View &src,const View &dst,const ScalePlan &plan,uint32_t blend_mask,
+  uint32_t store_mask,int alpha);
 MhStatus launch_wavelet_denoise(const View &src,const View &dst,double threshold,double softness,
   const Roles &roles);
 void release_color_tables();          // frees the per-device transfer-function tables

@@ -8,6 +8,7 @@
 
 #include <cstdio>
 #include "resize_filter.hpp"
+#include "scale_plan.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -46,7 +47,9 @@ struct Pair
 {
   DeviceGuard guard;         // declared first: the device is restored after src/dst are gone
   Resident src,dst;
-  MhStatus open(const MhImage *image,MhImage *out)
+  // keep_destination: the operator leaves some channels of `out` as they are, so a host destination is
+  // brought to the device too (Resident mode 2) instead of starting from unset memory
+  MhStatus open(const MhImage *image,MhImage *out,bool keep_destination=false)
   {
     int device=resolve_device(image->memory == MH_MEMORY_DEVICE ? image : out);
     hipStream_t stream;
@@ -57,7 +60,7 @@ struct Pair
     else
       stream=library_stream(device);
     MH_TRY(src.open(image,0,stream,device));
-    MH_TRY(dst.open(out,1,stream,device));
+    MH_TRY(dst.open(out,keep_destination ? 2 : 1,stream,device));
     src.view.stream=stream;
     dst.view.stream=stream;
     src.view.device=device;
@@ -1511,6 +1514,140 @@ MH_API MhStatus MagickHipResizeImage(const MhImage *image,MhImage *resize_image,
   MhStatus status=MagickHipResizeImageWithFilter(image,resize_image,f);
   MhDestroyResizeFilter(f);
   return status;
+}
+
+
+// the reference's same-size early return (CloneImage, resize.c:3944-3945, :4156-4157, :4615)
+static MhStatus copy_same_size(const MhImage *image,MhImage *out)
+{
+  Pair pair;
+  MH_TRY(pair.open(image,out));
+  MH_TRY(launch_copy(pair.src.view,pair.dst.view));
+  return pair.commit();
+}
+
+// channels whose trait is defined in the source and in the destination: the only ones SampleImage and
+// ScaleImage store (resize.c:4048-4050, :4396-4398)
+static uint32_t defined_channels(const MhImage *image,const MhImage *out)
+{
+  uint32_t mask=0;
+  for (uint32_t c=0; c < image->number_channels; c++)
+    if ((image->channel_traits[c] != MH_TRAIT_UNDEFINED) && (out->channel_traits[c] != MH_TRAIT_UNDEFINED))
+      mask|=1u << c;
+  return mask;
+}
+
+static uint32_t all_channels(const MhImage *image)
+{
+  return (1u << image->number_channels)-1u;
+}
+
+// SampleImage, resize.c:3907-4075
+MH_API MhStatus MagickHipSampleImage(const MhImage *image,MhImage *sample_image,double offset_x_percent,
+  double offset_y_percent)
+{
+  MH_TRY(gate_pair(image,sample_image,"SampleImage",false));
+  if ((sample_image->columns == image->columns) && (sample_image->rows == image->rows))
+    return copy_same_size(image,sample_image);
+  std::vector<long long> x_offset,y_offset;
+  if (!sample_offsets(image->columns,sample_image->columns,offset_x_percent,x_offset) ||
+      !sample_offsets(image->rows,sample_image->rows,offset_y_percent,y_offset))
+    return fail(MH_UNSUPPORTED,"SampleImage: sample:offset %g%%x%g%% reads virtual pixels",offset_x_percent,
+      offset_y_percent);
+  const uint32_t stored=defined_channels(image,sample_image);
+  Pair pair;
+  MH_TRY(pair.open(image,sample_image,stored != all_channels(image)));
+  TableBundle tables;
+  const size_t x_slot=tables.add(x_offset.data(),x_offset.size()*sizeof(long long));
+  const size_t y_slot=tables.add(y_offset.data(),y_offset.size()*sizeof(long long));
+  MH_TRY(tables.upload(pair.src.view.device,pair.src.view.stream));
+  MH_TRY(launch_sample(pair.src.view,pair.dst.view,tables.at<long long>(x_slot),tables.at<long long>(y_slot),stored));
+  return pair.commit();
+}
+
+// ScaleImage, resize.c:4106-4536
+MH_API MhStatus MagickHipScaleImage(const MhImage *image,MhImage *scale_image)
+{
+  MH_TRY(gate_pair(image,scale_image,"ScaleImage",false));
+  if ((scale_image->columns == image->columns) && (scale_image->rows == image->rows))
+    return copy_same_size(image,scale_image);
+  ScalePlan plan;
+  plan.rows=scale_axis_plan(image->rows,scale_image->rows,0);
+  plan.columns=scale_axis_plan(image->columns,scale_image->columns,1);
+  if (!plan.rows.valid || !plan.columns.valid)
+    return fail(MH_UNSUPPORTED,"ScaleImage: %zux%zu -> %zux%zu leaves a destination column unset or stores past the "
+      "scanline in the reference",image->columns,image->rows,scale_image->columns,scale_image->rows);
+  // resize.c:4246-4257: alpha weights the channels that carry Blend, whatever the destination's traits
+  uint32_t blend_mask=0;
+  for (uint32_t c=0; c < image->number_channels; c++)
+    if ((image->channel_traits[c] & MH_TRAIT_BLEND) != 0)
+      blend_mask|=1u << c;
+  const int alpha=image->alpha_trait != MH_TRAIT_UNDEFINED ? image->alpha_offset : -1;
+  const uint32_t stored=defined_channels(image,scale_image);
+  Pair pair;
+  MH_TRY(pair.open(image,scale_image,stored != all_channels(image)));
+  MH_TRY(launch_scale(pair.src.view,pair.dst.view,plan,blend_mask,stored,alpha));
+  return pair.commit();
+}
+
+// ThumbnailImage's pixel work, resize.c:4618-4653
+MH_API MhStatus MagickHipThumbnailImage(const MhImage *image,MhImage *thumbnail_image,MhFilterType filter)
+{
+  MH_TRY(gate_pair(image,thumbnail_image,"ThumbnailImage",false));
+  const size_t columns=thumbnail_image->columns,rows=thumbnail_image->rows;
+  if ((columns == image->columns) && (rows == image->rows))
+    return copy_same_size(image,thumbnail_image);
+  if ((columns > 0x3fffffffu) || (rows > 0x3fffffffu))
+    return fail(MH_UNSUPPORTED,"ThumbnailImage: a thumbnail side above 2^30");
+  const ptrdiff_t x_factor=(ptrdiff_t) image->columns/(ptrdiff_t) columns;
+  const ptrdiff_t y_factor=(ptrdiff_t) image->rows/(ptrdiff_t) rows;
+  Pair pair;
+  MH_TRY(pair.open(image,thumbnail_image));
+  // the stages see device-resident descriptors on the call's stream: nothing is read back in between
+  const auto resident=[](const MhImage &like,const View &view)
+  {
+    MhImage d=like;
+    d.pixels=view.pixels;
+    d.memory=MH_MEMORY_DEVICE;
+    d.device=view.device;
+    d.stream=(void *) view.stream;
+    return d;
+  };
+  MhImage current=resident(*image,pair.src.view);
+  MhImage result=resident(*thumbnail_image,pair.dst.view);
+  Temp sampled,boxed;
+  const auto intermediate=[&](Temp &memory,size_t factor,MhImage &next)
+  {
+    next=current;
+    next.columns=factor*columns;
+    next.rows=factor*rows;
+    View view=pair.src.view;
+    view.columns=next.columns;
+    view.rows=next.rows;
+    MH_TRY(memory.alloc(view.device,view.bytes(),view.stream));
+    next.pixels=memory.ptr;
+    return MhStatus(MH_OK);
+  };
+  if ((x_factor > 4) && (y_factor > 4))
+    {
+      MhImage next;
+      MH_TRY(intermediate(sampled,4,next));
+      MH_TRY(MagickHipSampleImage(&current,&next,-1.0,-1.0));
+      current=next;
+    }
+  if ((x_factor > 2) && (y_factor > 2))
+    {
+      // its Quantum-rounded result feeds the final filter: bit-identical in either mode, as the first of
+      // ResizeImage's own two filters is
+      MhImage next;
+      MH_TRY(intermediate(boxed,2,next));
+      MhImage pinned=current;
+      pinned.precision=MH_IMAGE_PRECISION(MH_PRECISION_EXACT);
+      MH_TRY(MagickHipResizeImage(&pinned,&next,MH_FILTER_BOX));
+      current=next;
+    }
+  MH_TRY(MagickHipResizeImage(&current,&result,filter == MH_FILTER_UNDEFINED ? MH_FILTER_LANCZOSSHARP : filter));
+  return pair.commit();
 }
 
 } // extern "C"

@@ -595,6 +595,39 @@ MH_API MhStatus MagickHipResizeImage(const MhImage *image,MhImage *resize_image,
 MH_API MhStatus MagickHipResizeImageWithFilter(const MhImage *image,MhImage *resize_image,
   const MhResizeFilter *filter);
 
+/* SampleImage, resize.c:3907-4075: sample_image carries the target columns/rows.  Every defined channel
+   is copied verbatim from column (ssize_t) (((x+offset)*columns)/sample_columns), rows alike, with
+   offset = percent/100-MagickEpsilon (the sample:offset artifact); a negative percentage means the
+   default, 0.5-MagickEpsilon.  Percentages above 100, and any geometry whose offsets leave the frame,
+   would read virtual pixels: MH_UNSUPPORTED, destination untouched.  A same-size request copies.
+   Bit-identical in both precision modes. */
+MH_API MhStatus MagickHipSampleImage(const MhImage *image,MhImage *sample_image,double offset_x_percent,
+  double offset_y_percent);
+/* ScaleImage, resize.c:4106-4536: the reference's two serial state machines depend on the four
+   dimensions only, so every output sample is a short ordered fp64 sum whose terms a host plan lists
+   (MhScaleImagePlan); the device evaluates them in the reference's order.  Bit-identical in both
+   precision modes, Q16 and float Quantum.  A same-size request copies.  MH_UNSUPPORTED (destination
+   untouched) for a geometry in which the reference leaves a destination column unset or stores past its
+   scanline; none is known. */
+MH_API MhStatus MagickHipScaleImage(const MhImage *image,MhImage *scale_image);
+/* ThumbnailImage's pixel work, resize.c:4627-4649: with the integer factors columns/thumbnail columns
+   and rows/thumbnail rows both above 4 SampleImage to four times the target, both above 2
+   ResizeImage(Box) to twice the target, then ResizeImage(filter) to the target (MH_FILTER_UNDEFINED:
+   LanczosSharp).  The intermediates stay on the device.  When both resizes run, the Box stage runs in
+   MH_PRECISION_EXACT whatever the mode, so the result keeps ResizeImage's contract. */
+MH_API MhStatus MagickHipThumbnailImage(const MhImage *image,MhImage *thumbnail_image,MhFilterType filter);
+/* ScaleImage's plan for one axis (host only, no device needed).  axis 0: rows (the y_vector / span.y
+   machine), axis 1: columns (the scale_scanline machine).  counts[d] receives the number of terms of
+   destination sample d; indices / weights receive the terms of sample 0, then sample 1, ... in the order
+   the reference adds them, each sum starting from 0.0; at most `capacity` terms are written.  An axis
+   with source == destination has no terms: the reference does no arithmetic there.  Returns the total
+   number of terms, -1 for a zero dimension, -2 when the plan is not realisable (see MagickHipScaleImage). */
+MH_API long long MhScaleImagePlan(size_t source,size_t destination,int axis,unsigned *counts,int *indices,
+  double *weights,size_t capacity);
+/* SampleImage's offset table for one axis (host only); returns 0, or -1 when an offset leaves
+   [0, source) or the percentage is above 100 (negative: the default). */
+MH_API int MhSampleImageOffsets(size_t source,size_t destination,double offset_percent,long long *offsets);
+
 /* AccelerateContrastStretchImage: ContrastStretchImage, enhance.c:1544-1818.
    black_point / white_point are pixel counts as in the MagickCore API.
    *became_gray (optional) reports the IdentifyImageType side effect
@@ -925,8 +958,12 @@ typedef enum
                                   MagickHipShardedImage runs them band by band, no halo, no collective */
   MH_OP_AUTO_LEVEL = 22,
   MH_OP_LINEAR_STRETCH = 23,   /* args: black_point, white_point (pixel counts) */
-  MH_OP_NORMALIZE = 24         /* These three: MagickHipBatchImages only; MagickHipShardedImage returns
+  MH_OP_NORMALIZE = 24,        /* These three: MagickHipBatchImages only; MagickHipShardedImage returns
                                   MH_UNSUPPORTED (the bands' range or counts would have to be all-reduced) */
+  MH_OP_SAMPLE = 25,           /* args: columns, rows (default sample:offset) */
+  MH_OP_SCALE = 26,            /* args: columns, rows */
+  MH_OP_THUMBNAIL = 27         /* args: columns, rows, MhFilterType.  These three change the geometry like
+                                  MH_OP_RESIZE: batch only, and the chain needs result descriptors */
 } MhOperatorKind;
 
 typedef struct MhOperator

@@ -46,6 +46,7 @@
 #include "MagickCore/property.h"
 #include "MagickCore/magick.h"
 #include "MagickCore/threshold.h"
+#include "MagickCore/geometry.h"
 
 #if defined(MAGICKCORE_OPENCL_SUPPORT)
 
@@ -631,6 +632,83 @@ MagickPrivate Image *AccelerateResizeImage(const Image *image,
   resize_image->type=image->type;    /* resize.c:3872 */
   HipAccepted(image);
   return(resize_image);
+}
+
+/*
+  SampleImage and ScaleImage: the shim's own hooks (shim/patch_hooks.py), each in front of the sized
+  CloneImage (resize.c:3946, :4158), so behind the same-size early return.  ThumbnailImage
+  (resize.c:4591) has none: SampleImage -> ResizeImage(Box) -> ResizeImage all arrive here, and its
+  frame stays on the device from the one upload of the source to the download of the thumbnail.
+  sample:offset is parsed as the reference parses it (resize.c:3958-3972); an offset outside
+  [0, 100] % indexes virtual pixels and stays on the CPU.
+*/
+MagickPrivate Image *AccelerateSampleImage(const Image *image,const size_t columns,const size_t rows,
+  ExceptionInfo *exception)
+{
+  const char
+    *value;
+
+  double
+    x_percent,
+    y_percent;
+
+  HipCall
+    call;
+
+  Image
+    *sample_image;
+
+  if ((IsImageAcceleratable(image) == MagickFalse) || (columns == 0) || (rows == 0))
+    return(HipDeclined(image,(Image *) NULL));
+  x_percent=(-1.0);     /* the default: the mid-point of the sample regions */
+  y_percent=(-1.0);
+  value=GetImageArtifact(image,"sample:offset");
+  if (value != (const char *) NULL)
+    {
+      GeometryInfo
+        geometry_info;
+
+      MagickStatusType
+        flags;
+
+      flags=ParseGeometry(value,&geometry_info);
+      x_percent=geometry_info.rho;
+      y_percent=geometry_info.rho;
+      if ((flags & SigmaValue) != 0)
+        y_percent=geometry_info.sigma;
+      if (!((x_percent >= 0.0) && (x_percent <= 100.0) && (y_percent >= 0.0) && (y_percent <= 100.0)))
+        return(HipDeclined(image,(Image *) NULL));
+    }
+  if (BeginHipCall(&call,image,columns,rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  sample_image=EndHipCall(&call,call.library->SampleImage(&call.source,&call.destination,x_percent,y_percent));
+  if (sample_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  sample_image->type=image->type;    /* resize.c:4071 */
+  HipAccepted(image);
+  return(sample_image);
+}
+
+MagickPrivate Image *AccelerateScaleImage(const Image *image,const size_t columns,const size_t rows,
+  ExceptionInfo *exception)
+{
+  HipCall
+    call;
+
+  Image
+    *scale_image;
+
+  if ((IsImageAcceleratable(image) == MagickFalse) || (columns == 0) || (rows == 0))
+    return(HipDeclined(image,(Image *) NULL));
+  /* the result is DirectClass, as resize.c:4161 makes it (BeginHipCall) */
+  if (BeginHipCall(&call,image,columns,rows,exception) == MagickFalse)
+    return(HipDeclined(image,(Image *) NULL));
+  scale_image=EndHipCall(&call,call.library->ScaleImage(&call.source,&call.destination));
+  if (scale_image == (Image *) NULL)
+    return(HipDeclined(image,(Image *) NULL));
+  scale_image->type=image->type;     /* resize.c:4532 */
+  HipAccepted(image);
+  return(scale_image);
 }
 
 /* EqualizeImage / ContrastStretchImage of one big host-resident image, in place, one row band per

@@ -60,6 +60,8 @@ typedef struct _HipLibrary
   MhStatus (*SigmoidalContrastImage)(MhImage *,int,double,double);
   MhStatus (*MinMaxStretchImage)(MhImage *,double,double,double);
   MhStatus (*LinearStretchImage)(MhImage *,double,double,size_t *,size_t *);
+  MhStatus (*SampleImage)(const MhImage *,MhImage *,double,double);
+  MhStatus (*ScaleImage)(const MhImage *,MhImage *);
   MhStatus (*LocalContrastImage)(const MhImage *,MhImage *,double,double);
   MhStatus (*RotationalBlurImage)(const MhImage *,MhImage *,double);
   MhStatus (*ContrastImage)(MhImage *,int);

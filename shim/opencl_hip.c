@@ -189,6 +189,8 @@ static void LoadHipLibrary(void)
   MH_RESOLVE(SigmoidalContrastImage,"MagickHipSigmoidalContrastImage");
   MH_RESOLVE(MinMaxStretchImage,"MagickHipMinMaxStretchImage");
   MH_RESOLVE(LinearStretchImage,"MagickHipLinearStretchImage");
+  MH_RESOLVE(SampleImage,"MagickHipSampleImage");
+  MH_RESOLVE(ScaleImage,"MagickHipScaleImage");
   MH_RESOLVE(LocalContrastImage,"MagickHipLocalContrastImage");
   MH_RESOLVE(RotationalBlurImage,"MagickHipRotationalBlurImage");
   MH_RESOLVE(ContrastImage,"MagickHipContrastImage");

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Generates, at build time, copies of eight MagickCore sources with the accelerate call
+"""Generates, at build time, copies of nine MagickCore sources with the accelerate call
 sites the reference does not have (or has commented out) switched in — SURVEY 8b: "new hooks
 for Morphology and Colorspace", the disabled UnsharpMask stanza, the caller-less
 ContrastStretch, WaveletDenoise's hook without its softness argument — and a hook that
 StatisticImage, BilateralBlurImage, SelectiveBlurImage, KuwaharaImage, CLAHEImage, AdaptiveThresholdImage, BilevelImage,
-AutoThresholdImage, LevelImage, LevelizeImage, GammaImage, NegateImage, SigmoidalContrastImage, LinearStretchImage and
-MinMaxStretchImage lack altogether.  Each hook is the reference's own three-line idiom
+AutoThresholdImage, LevelImage, LevelizeImage, GammaImage, NegateImage, SigmoidalContrastImage, LinearStretchImage,
+MinMaxStretchImage, SampleImage and ScaleImage lack altogether.  Each hook is the reference's own three-line idiom
 (effect.c:783-787).  The copies are written under shim/_build/ (never committed, never
 shipped); the reference tree is only read.
 
@@ -83,6 +83,13 @@ extern MagickPrivate Image *AccelerateAdaptiveThresholdImage(const Image *,const
 extern MagickPrivate MagickBooleanType AccelerateBilevelImage(Image *,const double,ExceptionInfo *);
 extern MagickPrivate MagickBooleanType AccelerateAutoThresholdImage(Image *,const AutoThresholdMethod,
   ExceptionInfo *);
+#endif
+'''
+
+RESIZE_PROTOTYPE = '''
+#if defined(MAGICKCORE_OPENCL_SUPPORT)
+extern MagickPrivate Image *AccelerateSampleImage(const Image *,const size_t,const size_t,ExceptionInfo *);
+extern MagickPrivate Image *AccelerateScaleImage(const Image *,const size_t,const size_t,ExceptionInfo *);
 #endif
 '''
 
@@ -270,12 +277,29 @@ def histogram(text):
 ''' + anchor, "histogram.c")
 
 
+def resize(text):
+    # SampleImage and ScaleImage have no accelerate hook in the reference: one in front of the sized
+    # CloneImage of each, behind the same-size early return.  ThumbnailImage needs none: its three
+    # callees are SampleImage and ResizeImage, and its frame stays on the device between them.
+    text = after_includes(text, RESIZE_PROTOTYPE)
+    for function, result in (("SampleImage(", "sample_image"), ("ScaleImage(", "scale_image")):
+        anchor = "  %s=CloneImage(image,columns,rows,MagickTrue,exception);\n" % result
+        text = in_function(text, "MagickExport Image *" + function, anchor, '''#if defined(MAGICKCORE_OPENCL_SUPPORT)
+  %s=Accelerate%simage,columns,rows,exception);
+  if (%s != (Image *) NULL)
+    return(%s);
+#endif
+''' % (result, function, result, result) + anchor, "resize.c")
+    return text
+
+
 def main():
     source, out = sys.argv[1], sys.argv[2]
     os.makedirs(out, exist_ok=True)
     for name, fn in (("morphology.c", morphology), ("effect.c", effect), ("enhance.c", enhance),
                      ("colorspace.c", colorspace), ("visual-effects.c", visual_effects),
-                     ("statistic.c", statistic), ("threshold.c", threshold), ("histogram.c", histogram)):
+                     ("statistic.c", statistic), ("threshold.c", threshold), ("histogram.c", histogram),
+                     ("resize.c", resize)):
         text = open(os.path.join(source, name), encoding="latin-1").read()
         patched = fn(text)
         with open(os.path.join(out, name), "w", encoding="latin-1") as f:
