@@ -13,6 +13,9 @@ Outputs
                           implementation (oracle/_ref = MagickCore compiled from
                           /root/reference) for every operator on the hot path, Q16 and
                           Q16-HDRI; plus host-side tables (blur taps, resize filter weights).
+  resize_filter_vectors.npz  support and weights of every named resize filter but Jinc, as the
+                          reference's AcquireResizeFilter / GetResizeFilterWeight give them
+                          (`python tests/golden/make_golden.py resize_filters` writes this one alone).
 """
 import os
 import sys
@@ -203,8 +206,42 @@ def reference_vectors():
     print("reference_vectors.npz: %d arrays" % len(out))
 
 
+def resize_filter_grid(supports):
+    """The abscissae of resize_filter_vectors.npz: k/40 for |k| <= 210 (0, the half-integers and the
+    whole-number supports are exact binary fractions, and 5.25 lies beyond the widest support, 4.5),
+    plus every filter's own support and its two neighbouring doubles, on both sides of 0."""
+    xs = set((np.arange(-210, 211) / 40.0).tolist())
+    for s in supports:
+        for v in (s, np.nextafter(s, 0.0), np.nextafter(s, 10.0)):
+            xs.update((float(v), -float(v)))
+    return np.array(sorted(xs), dtype=np.float64)
+
+
+def resize_filter_vectors():
+    """Every named filter the product builds (all of imagemagick_amd/_lib.py::FILTERS but Undefined and
+    the cylindrical Jinc): GetResizeFilterSupport and GetResizeFilterWeight on one shared grid."""
+    from imagemagick_amd import _lib
+    from oracle import ref
+    names = [n for n in _lib.FILTERS if n not in ("undefined", "jinc")]
+    img = ref.RefImage(np.zeros((2, 2, 4), np.uint16))
+    supports = [img.filter_weights(n, np.zeros(1))[1] for n in names]
+    xs = resize_filter_grid(supports)
+    out = {"names": np.array(names), "xs": xs}
+    for n, support in zip(names, supports):
+        w, s = img.filter_weights(n, xs)
+        assert s == support
+        out["weights|" + n] = w
+        out["support|" + n] = np.array([s])
+    np.savez_compressed(os.path.join(HERE, "resize_filter_vectors.npz"), **out)
+    print("resize_filter_vectors.npz: %d filters, %d abscissae" % (len(names), xs.size))
+
+
 if __name__ == "__main__":
     if not os.path.isdir(REFERENCE):
         raise SystemExit("needs %s" % REFERENCE)
+    if sys.argv[1:] == ["resize_filters"]:          # this fixture alone; the others stay byte-identical
+        resize_filter_vectors()
+        raise SystemExit(0)
     perlmagick()
     reference_vectors()
+    resize_filter_vectors()
