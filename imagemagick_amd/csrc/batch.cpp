@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -71,22 +72,196 @@ static hipStream_t batch_stream(int physical,int index)
 }
 
 // ---------------------------------------------------------------- operators
+static size_t row_bytes(const MhImage &image)
+{
+  return image.columns*(size_t) image.number_channels*(image.quantum == MH_QUANTUM_U16 ? 2u : 4u);
+}
+
 static size_t image_bytes(const MhImage &image)
 {
-  return image.columns*image.rows*(size_t) image.number_channels*
-    (image.quantum == MH_QUANTUM_U16 ? 2u : 4u);
+  return row_bytes(image)*image.rows;
 }
+
+struct OperatorRow;
 
 // what an operator needs besides its arguments, built once per call
 struct PreparedOperator
 {
   MhOperator op;
+  const OperatorRow *row=nullptr;          // op.kind's row of g_rows
   std::unique_ptr<MhKernelInfo,MhKernelInfo *(*)(MhKernelInfo *)> kernel{nullptr,MhDestroyKernelInfo};
   const MhKernelInfo *borrowed=nullptr;   // a caller's kernel list (host_banded_operator)
   const MhKernelInfo *kernels() const { return borrowed != nullptr ? borrowed : kernel.get(); }
   size_t reach=0;              // rows a stencil reads above / below an output row
-  bool stencil=false,histogram=false;
 };
+
+// Everything the batch layer knows about an operator kind: one row of g_rows each.
+enum class Form
+{
+  IN_PLACE,                    // mutates the working image
+  NEW_IMAGE,                   // a pool buffer of the working image's geometry
+  NEW_GEOMETRY                 // a pool buffer of args[0] x args[1]: the chain needs result descriptors
+};
+
+struct OperatorRow
+{
+  uint32_t kind;               // the row's place in the table (checked below)
+  const char *name;            // for messages
+  Form form;
+  bool histogram;              // sharded: the bands' tables are all-reduced into one LUT
+  // `apply` casts args[size_first] .. args[size_first+size_count-1] to size_t: each within [0, size_limit]
+  int size_first,size_count;
+  double size_limit;
+  // a stencil: sets p.reach (morphology: and p.kernel); null: the operator reads no neighbouring rows
+  MhStatus (*reach)(PreparedOperator &p,size_t index);
+  // the public entry point; next: the result's descriptor, null for IN_PLACE
+  MhStatus (*apply)(const PreparedOperator &p,MhImage *image,MhImage *next);
+  const char *declined;        // why MagickHipShardedImage declines the kind; null: it shards
+  bool stencil() const { return reach != nullptr; }
+};
+
+static size_t half(size_t width)
+{
+  return (width-1)/2;
+}
+
+// a window of `side` rows reaches side/2 rows up and side-1-side/2 (<= side/2) down
+static size_t half_window(double side)
+{
+  const size_t rows=(size_t) side;
+  return (rows > 1 ? rows : 1)/2;
+}
+
+static MhStatus morphology_reach(PreparedOperator &p,size_t i)
+{
+  if (p.borrowed == nullptr)
+    {
+      if (p.op.text == nullptr)
+        return fail(MH_BAD_ARGUMENT,"operator %zu: morphology needs a kernel string",i);
+      p.kernel.reset(MhAcquireKernelInfo(p.op.text));
+      if (!p.kernel)
+        return fail(MH_BAD_ARGUMENT,"operator %zu: cannot parse kernel '%s'",i,p.op.text);
+    }
+  size_t reach=0;
+  for (const MhKernelInfo *k=p.kernels(); k != nullptr; k=k->next)
+    {
+      const size_t up=(size_t) k->y,down=k->height-1-(size_t) k->y;
+      reach+=up > down ? up : down;
+    }
+  // compound methods run up to four primitives per kernel (Smooth); iterations
+  // multiply the reach.  Iterate-until-convergence (-1) has no bound.
+  const ptrdiff_t iterations=(ptrdiff_t) p.op.args[1];
+  size_t stages=1;
+  switch ((MhMorphologyMethod) (int) p.op.args[0])
+  {
+    case MH_MORPHOLOGY_SMOOTH: stages=4; break;
+    case MH_MORPHOLOGY_OPEN: case MH_MORPHOLOGY_CLOSE: case MH_MORPHOLOGY_OPEN_INTENSITY:
+    case MH_MORPHOLOGY_CLOSE_INTENSITY: case MH_MORPHOLOGY_TOP_HAT:
+    case MH_MORPHOLOGY_BOTTOM_HAT: case MH_MORPHOLOGY_EDGE: stages=2; break;
+    default: break;
+  }
+  p.reach=iterations < 1 ? (size_t) -1 : reach*stages*(size_t) iterations;
+  return MH_OK;
+}
+
+#define MH_REACH(rows) \
+  [](PreparedOperator &p,size_t) -> MhStatus { const double *a=p.op.args; p.reach=(rows); return MH_OK; }
+#define MH_APPLY(call) \
+  [](const PreparedOperator &p,MhImage *image,MhImage *next) -> MhStatus \
+  { const double *a=p.op.args; (void) a; (void) next; return call; }
+// blur:RxS is 1 x W and W x 1 (effect.c:773)
+#define MH_BLUR_REACH MH_REACH(half(a[0] >= 1.0 ? (size_t) a[0]*2+1 : MhGetOptimalKernelWidth1D(a[0],a[1])))
+
+static constexpr double SIZE_U16=65535.0,SIZE_U32=4294967295.0;
+static constexpr char
+  DECLINED_GEOMETRY[]="ShardedImage: resize, sample, scale and thumbnail change the geometry",
+  DECLINED_CLAHE[]="ShardedImage: CLAHEImage's tile grid belongs to the whole frame",
+  DECLINED_THRESHOLD[]="ShardedImage: the threshold operators are not sharded (AutoThresholdImage needs the "
+    "bands' counts all-reduced, AdaptiveThresholdImage a halo)",
+  DECLINED_RANGE[]="ShardedImage: AutoLevelImage, LinearStretchImage and NormalizeImage are not sharded "
+    "(the bands' range or counts would have to be all-reduced)";
+
+static constexpr OperatorRow g_rows[]={
+  //  kind, name, form, histogram, size arguments (first, count, limit), reach, apply, declined
+  {MH_OP_BLUR,"blur",Form::NEW_IMAGE,false,0,0,0.0,MH_BLUR_REACH,
+    MH_APPLY(MagickHipBlurImage(image,next,a[0],a[1])),nullptr},
+  // GaussianBlurImage's kernel is Gaussian:RxS, (2*radius+1)^2 or GetOptimalKernelWidth2D (effect.c:1725)
+  {MH_OP_GAUSSIAN_BLUR,"gaussian blur",Form::NEW_IMAGE,false,0,0,0.0,
+    MH_REACH(half(a[0] >= 1.0 ? (size_t) a[0]*2+1 : MhGetOptimalKernelWidth2D(a[0],a[1]))),
+    MH_APPLY(MagickHipGaussianBlurImage(image,next,a[0],a[1])),nullptr},
+  {MH_OP_UNSHARP_MASK,"unsharp mask",Form::NEW_IMAGE,false,0,0,0.0,MH_BLUR_REACH,
+    MH_APPLY(MagickHipUnsharpMaskImage(image,next,a[0],a[1],a[2],a[3])),nullptr},
+  {MH_OP_RESIZE,"resize",Form::NEW_GEOMETRY,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipResizeImage(image,next,(MhFilterType) (int) a[2])),DECLINED_GEOMETRY},
+  {MH_OP_MORPHOLOGY,"morphology",Form::NEW_IMAGE,false,0,0,0.0,morphology_reach,
+    MH_APPLY(MagickHipMorphologyImage(image,next,(MhMorphologyMethod) (int) a[0],(ptrdiff_t) a[1],p.kernels(),a[2])),
+    nullptr},
+  {MH_OP_COLORSPACE,"colorspace",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipTransformImageColorspace(image,(MhColorspace) (int) a[0])),nullptr},
+  {MH_OP_CONTRAST_STRETCH,"contrast stretch",Form::IN_PLACE,true,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipContrastStretchImage(image,a[0],a[1],nullptr)),nullptr},
+  {MH_OP_EQUALIZE,"equalize",Form::IN_PLACE,true,0,0,0.0,nullptr,MH_APPLY(MagickHipEqualizeImage(image)),nullptr},
+  // StatisticImage's window: statistic.c:2979-2981
+  {MH_OP_STATISTIC,"statistic",Form::NEW_IMAGE,false,1,2,SIZE_U16,MH_REACH(half_window(a[2])),
+    MH_APPLY(MagickHipStatisticImage(image,next,(MhStatisticType) (int) a[0],(size_t) a[1],(size_t) a[2])),nullptr},
+  // BilateralBlurImage's window: effect.c:1022
+  {MH_OP_BILATERAL_BLUR,"bilateral blur",Form::NEW_IMAGE,false,0,2,SIZE_U16,MH_REACH(half_window(a[1])),
+    MH_APPLY(MagickHipBilateralBlurImage(image,next,(size_t) a[0],(size_t) a[1],a[2],a[3])),nullptr},
+  // SelectiveBlurImage's window is centred (effect.c:3559-3560)
+  {MH_OP_SELECTIVE_BLUR,"selective blur",Form::NEW_IMAGE,false,0,0,0.0,
+    MH_REACH(half(MhGetOptimalKernelWidth1D(a[0],a[1]))),
+    MH_APPLY(MagickHipSelectiveBlurImage(image,next,a[0],a[1],a[2])),nullptr},
+  // the blur's half width plus the selection's: a window reaches width-1 rows up or down, the
+  // interpolation width/2+1 rows down (effect.c:1809-1810, :1893-1951)
+  {MH_OP_KUWAHARA,"kuwahara",Form::NEW_IMAGE,false,0,1,SIZE_U16,
+    MH_REACH(half(MhGetOptimalKernelWidth1D(a[0],a[1]))+((size_t) a[0]+1)),
+    MH_APPLY(MagickHipKuwaharaImage(image,next,a[0],a[1])),nullptr},
+  {MH_OP_CLAHE,"clahe",Form::IN_PLACE,false,0,3,SIZE_U32,nullptr,
+    MH_APPLY(MagickHipCLAHEImage(image,(size_t) a[0],(size_t) a[1],(size_t) a[2],a[3])),DECLINED_CLAHE},
+  {MH_OP_THRESHOLD,"threshold",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipBilevelImage(image,a[0])),DECLINED_THRESHOLD},
+  {MH_OP_AUTO_THRESHOLD,"auto threshold",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipAutoThresholdImage(image,(MhAutoThresholdMethod) (int) a[0],nullptr)),DECLINED_THRESHOLD},
+  // no reach: the kind is batch only, and the host row-band pipeline does not take it
+  {MH_OP_ADAPTIVE_THRESHOLD,"adaptive threshold",Form::NEW_IMAGE,false,0,2,SIZE_U32,nullptr,
+    MH_APPLY(MagickHipAdaptiveThresholdImage(image,next,(size_t) a[0],(size_t) a[1],a[2])),DECLINED_THRESHOLD},
+  {MH_OP_LEVEL,"level",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipLevelImage(image,a[0],a[1],a[2])),nullptr},
+  {MH_OP_LEVELIZE,"levelize",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipLevelizeImage(image,a[0],a[1],a[2])),nullptr},
+  {MH_OP_GAMMA,"gamma",Form::IN_PLACE,false,0,0,0.0,nullptr,MH_APPLY(MagickHipGammaImage(image,a[0])),nullptr},
+  {MH_OP_NEGATE,"negate",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipNegateImage(image,a[0] != 0.0 ? 1 : 0)),nullptr},
+  {MH_OP_SIGMOIDAL_CONTRAST,"sigmoidal contrast",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipSigmoidalContrastImage(image,a[0] != 0.0 ? 1 : 0,a[1],a[2])),nullptr},
+  {MH_OP_AUTO_LEVEL,"auto level",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipAutoLevelImage(image)),DECLINED_RANGE},
+  {MH_OP_LINEAR_STRETCH,"linear stretch",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipLinearStretchImage(image,a[0],a[1],nullptr,nullptr)),DECLINED_RANGE},
+  {MH_OP_NORMALIZE,"normalize",Form::IN_PLACE,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipNormalizeImage(image)),DECLINED_RANGE},
+  {MH_OP_SAMPLE,"sample",Form::NEW_GEOMETRY,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipSampleImage(image,next,-1.0,-1.0)),DECLINED_GEOMETRY},
+  {MH_OP_SCALE,"scale",Form::NEW_GEOMETRY,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipScaleImage(image,next)),DECLINED_GEOMETRY},
+  {MH_OP_THUMBNAIL,"thumbnail",Form::NEW_GEOMETRY,false,0,0,0.0,nullptr,
+    MH_APPLY(MagickHipThumbnailImage(image,next,(MhFilterType) (int) a[2])),DECLINED_GEOMETRY}};
+#undef MH_BLUR_REACH
+#undef MH_APPLY
+#undef MH_REACH
+
+static constexpr size_t g_row_count=sizeof(g_rows)/sizeof(g_rows[0]);
+
+// row k-1 is kind k's
+static constexpr bool rows_follow_the_kinds()
+{
+  for (size_t i=0; i < g_row_count; i++)
+    if (g_rows[i].kind != i+1)
+      return false;
+  return true;
+}
+static_assert((g_row_count == MH_OP_THUMBNAIL) && rows_follow_the_kinds(),
+  "g_rows needs one row for every MhOperatorKind, in the order of the kinds, up to the last one (named here)");
 
 static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<PreparedOperator> &out,
   const MhKernelInfo *borrowed_kernel=nullptr)
@@ -97,119 +272,16 @@ static MhStatus prepare(const MhOperator *operators,size_t count,std::vector<Pre
       PreparedOperator &p=out[i];
       p.op=operators[i];
       p.borrowed=borrowed_kernel;
-      switch (p.op.kind)
-      {
-        case MH_OP_BLUR: case MH_OP_UNSHARP_MASK: case MH_OP_GAUSSIAN_BLUR:
-          {
-            // blur:RxS is 1 x W and W x 1 (effect.c:773); GaussianBlurImage's kernel is
-            // Gaussian:RxS, (2*radius+1)^2 or GetOptimalKernelWidth2D (effect.c:1725)
-            const double radius=p.op.args[0],sigma=p.op.args[1];
-            size_t width;
-            if (p.op.kind == MH_OP_GAUSSIAN_BLUR)
-              width=radius >= 1.0 ? (size_t) radius*2+1 : MhGetOptimalKernelWidth2D(radius,sigma);
-            else
-              width=radius >= 1.0 ? (size_t) radius*2+1 : MhGetOptimalKernelWidth1D(radius,sigma);
-            p.reach=(width-1)/2;
-            p.stencil=true;
-            break;
-          }
-        case MH_OP_MORPHOLOGY:
-          {
-            if (p.borrowed == nullptr)
-              {
-                if (p.op.text == nullptr)
-                  return fail(MH_BAD_ARGUMENT,"operator %zu: morphology needs a kernel string",i);
-                p.kernel.reset(MhAcquireKernelInfo(p.op.text));
-                if (!p.kernel)
-                  return fail(MH_BAD_ARGUMENT,"operator %zu: cannot parse kernel '%s'",i,p.op.text);
-              }
-            size_t reach=0,kernels=0;
-            for (const MhKernelInfo *k=p.kernels(); k != nullptr; k=k->next)
-              {
-                const size_t up=(size_t) k->y,down=k->height-1-(size_t) k->y;
-                reach+=up > down ? up : down;
-                kernels++;
-              }
-            // compound methods run up to four primitives per kernel (Smooth); iterations
-            // multiply the reach.  Iterate-until-convergence (-1) has no bound.
-            const ptrdiff_t iterations=(ptrdiff_t) p.op.args[1];
-            size_t stages=1;
-            switch ((MhMorphologyMethod) (int) p.op.args[0])
-            {
-              case MH_MORPHOLOGY_SMOOTH: stages=4; break;
-              case MH_MORPHOLOGY_OPEN: case MH_MORPHOLOGY_CLOSE: case MH_MORPHOLOGY_OPEN_INTENSITY:
-              case MH_MORPHOLOGY_CLOSE_INTENSITY: case MH_MORPHOLOGY_TOP_HAT:
-              case MH_MORPHOLOGY_BOTTOM_HAT: case MH_MORPHOLOGY_EDGE: stages=2; break;
-              default: break;
-            }
-            p.reach=iterations < 1 ? (size_t) -1 : reach*stages*(size_t) iterations;
-            p.stencil=true;
-            (void) kernels;
-            break;
-          }
-        case MH_OP_STATISTIC:
-          {
-            // StatisticImage's window reaches H/2 rows up and H-1-H/2 (<= H/2) down
-            // (statistic.c:2979-2981)
-            if (!(p.op.args[1] >= 0.0) || (p.op.args[1] > 65535.0) || !(p.op.args[2] >= 0.0) ||
-                (p.op.args[2] > 65535.0))
-              return fail(MH_BAD_ARGUMENT,"operator %zu: statistic window %gx%g",i,p.op.args[1],p.op.args[2]);
-            const size_t height=(size_t) p.op.args[2];
-            p.reach=(height > 1 ? height : 1)/2;
-            p.stencil=true;
-            break;
-          }
-        case MH_OP_BILATERAL_BLUR:
-          {
-            // BilateralBlurImage's window reaches H/2 rows up and down (effect.c:1022)
-            if (!(p.op.args[0] >= 0.0) || (p.op.args[0] > 65535.0) || !(p.op.args[1] >= 0.0) ||
-                (p.op.args[1] > 65535.0))
-              return fail(MH_BAD_ARGUMENT,"operator %zu: bilateral window %gx%g",i,p.op.args[0],p.op.args[1]);
-            const size_t height=(size_t) p.op.args[1];
-            p.reach=(height > 1 ? height : 1)/2;
-            p.stencil=true;
-            break;
-          }
-        case MH_OP_SELECTIVE_BLUR:
-          // SelectiveBlurImage's window is centred (effect.c:3559-3560)
-          p.reach=(MhGetOptimalKernelWidth1D(p.op.args[0],p.op.args[1])-1)/2;
-          p.stencil=true;
-          break;
-        case MH_OP_KUWAHARA:
-          {
-            // the blur's half width plus the selection's: a window reaches width-1 rows up or down, the
-            // interpolation width/2+1 rows down (effect.c:1809-1810, :1893-1951)
-            if (!(p.op.args[0] >= 0.0) || (p.op.args[0] > 65535.0))
-              return fail(MH_BAD_ARGUMENT,"operator %zu: kuwahara radius %g",i,p.op.args[0]);
-            p.reach=(MhGetOptimalKernelWidth1D(p.op.args[0],p.op.args[1])-1)/2+((size_t) p.op.args[0]+1);
-            p.stencil=true;
-            break;
-          }
-        case MH_OP_RESIZE: case MH_OP_COLORSPACE: case MH_OP_SAMPLE: case MH_OP_SCALE: case MH_OP_THUMBNAIL:
-          break;
-        case MH_OP_CLAHE:
-          // width, height, number_bins are size_t arguments of the call
-          for (int k=0; k < 3; k++)
-            if (!(p.op.args[k] >= 0.0) || (p.op.args[k] > 4294967295.0))
-              return fail(MH_BAD_ARGUMENT,"operator %zu: clahe argument %d is %g",i,k,p.op.args[k]);
-          break;
-        case MH_OP_CONTRAST_STRETCH: case MH_OP_EQUALIZE:
-          p.histogram=true;
-          break;
-        case MH_OP_THRESHOLD: case MH_OP_AUTO_THRESHOLD:
-          break;
-        case MH_OP_LEVEL: case MH_OP_LEVELIZE: case MH_OP_GAMMA: case MH_OP_NEGATE: case MH_OP_SIGMOIDAL_CONTRAST:
-        case MH_OP_AUTO_LEVEL: case MH_OP_LINEAR_STRETCH: case MH_OP_NORMALIZE:
-          break;
-        case MH_OP_ADAPTIVE_THRESHOLD:
-          // width and height are size_t arguments of the call
-          for (int k=0; k < 2; k++)
-            if (!(p.op.args[k] >= 0.0) || (p.op.args[k] > 4294967295.0))
-              return fail(MH_BAD_ARGUMENT,"operator %zu: adaptive threshold argument %d is %g",i,k,p.op.args[k]);
-          break;
-        default:
-          return fail(MH_BAD_ARGUMENT,"operator %zu: unknown kind %u",i,p.op.kind);
-      }
+      if ((p.op.kind < 1) || (p.op.kind > g_row_count))
+        return fail(MH_BAD_ARGUMENT,"operator %zu: unknown kind %u",i,p.op.kind);
+      const OperatorRow &row=g_rows[p.op.kind-1];
+      p.row=&row;
+      for (int k=row.size_first; k < row.size_first+row.size_count; k++)
+        if (!(p.op.args[k] >= 0.0) || (p.op.args[k] > row.size_limit))
+          return fail(MH_BAD_ARGUMENT,"operator %zu: %s argument %d is %g, not a size of 0 to %.0f",i,row.name,k,
+            p.op.args[k],row.size_limit);
+      if (row.reach != nullptr)
+        MH_TRY(row.reach(p,i));
     }
   return MH_OK;
 }
@@ -229,52 +301,15 @@ struct Working
   }
 };
 
-// the operators whose result has the geometry of args[0] x args[1]
-static bool changes_geometry(uint32_t kind)
-{
-  return (kind == MH_OP_RESIZE) || (kind == MH_OP_SAMPLE) || (kind == MH_OP_SCALE) || (kind == MH_OP_THUMBNAIL);
-}
-
 // One operator on `cur`.  New-image operators allocate their result from the pool and release
 // their input; in-place operators mutate cur.  Everything is enqueued on cur.stream.
 static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
 {
   const MhOperator &op=p.op;
-  switch (op.kind)
-  {
-    case MH_OP_COLORSPACE:
-      return MagickHipTransformImageColorspace(&cur.image,(MhColorspace) (int) op.args[0]);
-    case MH_OP_CONTRAST_STRETCH:
-      return MagickHipContrastStretchImage(&cur.image,op.args[0],op.args[1],nullptr);
-    case MH_OP_EQUALIZE:
-      return MagickHipEqualizeImage(&cur.image);
-    case MH_OP_CLAHE:
-      return MagickHipCLAHEImage(&cur.image,(size_t) op.args[0],(size_t) op.args[1],(size_t) op.args[2],op.args[3]);
-    case MH_OP_THRESHOLD:
-      return MagickHipBilevelImage(&cur.image,op.args[0]);
-    case MH_OP_AUTO_THRESHOLD:
-      return MagickHipAutoThresholdImage(&cur.image,(MhAutoThresholdMethod) (int) op.args[0],nullptr);
-    case MH_OP_LEVEL:
-      return MagickHipLevelImage(&cur.image,op.args[0],op.args[1],op.args[2]);
-    case MH_OP_LEVELIZE:
-      return MagickHipLevelizeImage(&cur.image,op.args[0],op.args[1],op.args[2]);
-    case MH_OP_GAMMA:
-      return MagickHipGammaImage(&cur.image,op.args[0]);
-    case MH_OP_NEGATE:
-      return MagickHipNegateImage(&cur.image,op.args[0] != 0.0 ? 1 : 0);
-    case MH_OP_SIGMOIDAL_CONTRAST:
-      return MagickHipSigmoidalContrastImage(&cur.image,op.args[0] != 0.0 ? 1 : 0,op.args[1],op.args[2]);
-    case MH_OP_AUTO_LEVEL:
-      return MagickHipAutoLevelImage(&cur.image);
-    case MH_OP_LINEAR_STRETCH:
-      return MagickHipLinearStretchImage(&cur.image,op.args[0],op.args[1],nullptr,nullptr);
-    case MH_OP_NORMALIZE:
-      return MagickHipNormalizeImage(&cur.image);
-    default:
-      break;
-  }
+  if (p.row->form == Form::IN_PLACE)
+    return p.row->apply(p,&cur.image,nullptr);
   MhImage next=cur.image;
-  if (changes_geometry(op.kind))
+  if (p.row->form == Form::NEW_GEOMETRY)
     {
       if (!(op.args[0] >= 1.0) || !(op.args[1] >= 1.0) || (op.args[0] > 4294967295.0) || (op.args[1] > 4294967295.0))
         return fail(MH_BAD_ARGUMENT,"operator %u: a result of %gx%g",op.kind,op.args[0],op.args[1]);
@@ -284,54 +319,7 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
   void *memory=nullptr;
   MH_TRY(pool_alloc(cur.device,image_bytes(next),cur.stream,&memory));
   next.pixels=memory;
-  MhStatus status=MH_BAD_ARGUMENT;
-  switch (op.kind)
-  {
-    case MH_OP_BLUR:
-      status=MagickHipBlurImage(&cur.image,&next,op.args[0],op.args[1]);
-      break;
-    case MH_OP_GAUSSIAN_BLUR:
-      status=MagickHipGaussianBlurImage(&cur.image,&next,op.args[0],op.args[1]);
-      break;
-    case MH_OP_UNSHARP_MASK:
-      status=MagickHipUnsharpMaskImage(&cur.image,&next,op.args[0],op.args[1],op.args[2],op.args[3]);
-      break;
-    case MH_OP_RESIZE:
-      status=MagickHipResizeImage(&cur.image,&next,(MhFilterType) (int) op.args[2]);
-      break;
-    case MH_OP_SAMPLE:
-      status=MagickHipSampleImage(&cur.image,&next,-1.0,-1.0);
-      break;
-    case MH_OP_SCALE:
-      status=MagickHipScaleImage(&cur.image,&next);
-      break;
-    case MH_OP_THUMBNAIL:
-      status=MagickHipThumbnailImage(&cur.image,&next,(MhFilterType) (int) op.args[2]);
-      break;
-    case MH_OP_STATISTIC:
-      status=MagickHipStatisticImage(&cur.image,&next,(MhStatisticType) (int) op.args[0],(size_t) op.args[1],
-        (size_t) op.args[2]);
-      break;
-    case MH_OP_BILATERAL_BLUR:
-      status=MagickHipBilateralBlurImage(&cur.image,&next,(size_t) op.args[0],(size_t) op.args[1],op.args[2],
-        op.args[3]);
-      break;
-    case MH_OP_SELECTIVE_BLUR:
-      status=MagickHipSelectiveBlurImage(&cur.image,&next,op.args[0],op.args[1],op.args[2]);
-      break;
-    case MH_OP_KUWAHARA:
-      status=MagickHipKuwaharaImage(&cur.image,&next,op.args[0],op.args[1]);
-      break;
-    case MH_OP_ADAPTIVE_THRESHOLD:
-      status=MagickHipAdaptiveThresholdImage(&cur.image,&next,(size_t) op.args[0],(size_t) op.args[1],op.args[2]);
-      break;
-    case MH_OP_MORPHOLOGY:
-      status=MagickHipMorphologyImage(&cur.image,&next,(MhMorphologyMethod) (int) op.args[0],
-        (ptrdiff_t) op.args[1],p.kernels(),op.args[2]);
-      break;
-    default:
-      break;
-  }
+  const MhStatus status=p.row->apply(p,&cur.image,&next);
   if (status != MH_OK)
     {
       pool_free(cur.device,memory,cur.stream);
@@ -341,6 +329,55 @@ static MhStatus apply_operator(const PreparedOperator &p,Working &cur)
   cur.image=next;
   cur.owned=true;
   return MH_OK;
+}
+
+// The first failure among worker threads: its status and its message (the last error is per thread).
+struct FirstError
+{
+  std::mutex lock;
+  MhStatus status=MH_OK;
+  std::string message;
+  void record(MhStatus failed)                  // on the thread that failed
+  {
+    if (failed == MH_OK)
+      return;
+    std::lock_guard<std::mutex> guard(lock);
+    if (status == MH_OK)
+      {
+        status=failed;
+        message=MhGetLastError();
+      }
+  }
+  MhStatus result() const
+  {
+    return status != MH_OK ? fail(status,"%s",message.c_str()) : MH_OK;
+  }
+};
+
+// work(0) here, work(1) .. work(count-1) on threads of their own; returns when all have
+template<typename Work> static void run_workers(size_t count,const Work &work)
+{
+  std::vector<std::thread> pool;
+  for (size_t w=1; w < count; w++)
+    pool.emplace_back(std::cref(work),w);
+  work(0);
+  for (std::thread &t : pool)
+    t.join();
+}
+
+// Rows [y0,y1) of `image` with up to `reach` halo rows on both sides, as far as the image has them.
+struct BandSlice
+{
+  MhImage image;               // rows y0-top .. y1+bottom
+  size_t top,bottom;
+};
+
+static BandSlice band_slice(const MhImage &image,size_t y0,size_t y1,size_t reach)
+{
+  BandSlice slice{image,y0 < reach ? y0 : reach,image.rows-y1 < reach ? image.rows-y1 : reach};
+  slice.image.rows=y1-y0+slice.top+slice.bottom;
+  slice.image.pixels=static_cast<char *>(image.pixels)+(y0-slice.top)*row_bytes(image);
+  return slice;
 }
 
 // A device-resident image belongs to the CALLER's stream (image.stream; null = the default
@@ -620,8 +657,7 @@ MhStatus host_banded_operator(const MhOperator &op,const MhKernelInfo *kernel,co
       (result->number_channels != image->number_channels) ||
       (memcmp(result->channel_traits,image->channel_traits,sizeof(image->channel_traits)) != 0))
     return MH_OK;
-  const size_t row_bytes=image->columns*(size_t) image->number_channels*
-    (image->quantum == MH_QUANTUM_U16 ? 2u : 4u);
+  const size_t row_bytes=mh::row_bytes(*image);
   size_t minimum=64u << 20;
   if (const char *e=option("MAGICKHIP_BANDED_MIN_BYTES"))
     minimum=(size_t) atoll(e);
@@ -631,7 +667,7 @@ MhStatus host_banded_operator(const MhOperator &op,const MhKernelInfo *kernel,co
   if (prepare(&op,1,chain,kernel) != MH_OK)
     return MH_OK;
   const size_t reach=chain[0].reach;
-  if (!chain[0].stencil || (reach == (size_t) -1) || (8*reach > image->rows))
+  if (!chain[0].row->stencil() || (reach == (size_t) -1) || (8*reach > image->rows))
     return MH_OK;
   // bands of ~32 MiB, at least four times the halo they carry
   size_t band_rows=(32u << 20)/row_bytes;
@@ -661,12 +697,10 @@ MhStatus host_banded_operator(const MhOperator &op,const MhKernelInfo *kernel,co
     }
   workers*=devices;
   std::atomic<size_t> next{0};
-  std::mutex error_lock;
-  MhStatus first_status=MH_OK;
-  std::string first_error;
-  auto work=[&](int w)
+  FirstError first;
+  auto work=[&](size_t index)
   {
-    const int logical=w % devices;
+    const int w=(int) index,logical=w % devices;
     const int device=spread ? logical % physical : first_device;
     DeviceGuard guard;
     hipStream_t stream=batch_stream(device,32+(spread ? w/devices+8*(logical/physical) : w));
@@ -680,44 +714,27 @@ MhStatus host_banded_operator(const MhOperator &op,const MhKernelInfo *kernel,co
           break;
         MhStatus status=setup;
         const size_t y0=b*band_rows,y1=y0+band_rows < H ? y0+band_rows : H;
-        const size_t top=y0 < reach ? y0 : reach,bottom=H-y1 < reach ? H-y1 : reach;
         Working cur;
         if (status == MH_OK)
           {
-            MhImage slice=*image;
-            slice.rows=y1-y0+top+bottom;
-            slice.pixels=static_cast<char *>(image->pixels)+(y0-top)*row_bytes;
-            status=working_copy(slice,device,stream,cur);
+            const BandSlice slice=band_slice(*image,y0,y1,reach);
+            status=working_copy(slice.image,device,stream,cur);
             if (status == MH_OK)
               status=apply_operator(chain[0],cur);
             if (status == MH_OK)
               status=MhDownload(device,static_cast<char *>(result->pixels)+y0*row_bytes,
-                static_cast<const char *>(cur.image.pixels)+top*row_bytes,(y1-y0)*row_bytes,stream);
+                static_cast<const char *>(cur.image.pixels)+slice.top*row_bytes,(y1-y0)*row_bytes,stream);
             else
               (void) hipStreamSynchronize(stream);
             cur.release();
             if (status == MH_OK)
               g_banded_bands[logical & 15].fetch_add(1,std::memory_order_relaxed);
           }
-        if (status != MH_OK)
-          {
-            std::lock_guard<std::mutex> lock(error_lock);
-            if (first_status == MH_OK)
-              {
-                first_status=status;
-                first_error=MhGetLastError();
-              }
-          }
+        first.record(status);
       }
   };
-  std::vector<std::thread> pool;
-  for (int w=1; w < workers; w++)
-    pool.emplace_back(work,w);
-  work(0);
-  for (std::thread &t : pool)
-    t.join();
-  if (first_status != MH_OK)
-    return fail(first_status,"%s",first_error.c_str());
+  run_workers((size_t) workers,work);
+  MH_TRY(first.result());
   *handled=true;
   return MH_OK;
 }
@@ -747,7 +764,7 @@ MH_API MhStatus MagickHipBatchImages(const MhOperator *operators,size_t number_o
   MH_TRY(prepare(operators,number_operators,chain));
   if (results == nullptr)
     for (const PreparedOperator &p : chain)
-      if (changes_geometry(p.op.kind))
+      if (p.row->form == Form::NEW_GEOMETRY)
         return fail(MH_BAD_ARGUMENT,"BatchImages: a chain that resizes needs result descriptors");
   for (size_t i=0; i < number_images; i++)
     {
@@ -762,9 +779,7 @@ MH_API MhStatus MagickHipBatchImages(const MhOperator *operators,size_t number_o
   if (workers > number_images)
     workers=number_images > 0 ? number_images : 1;
   std::atomic<size_t> next{0};
-  std::mutex error_lock;
-  MhStatus first_status=MH_OK;
-  std::string first_error;
+  FirstError first;
   std::vector<std::atomic<uint64_t>> counts(16);
   for (auto &c : counts)
     c=0;
@@ -838,41 +853,18 @@ MH_API MhStatus MagickHipBatchImages(const MhOperator *operators,size_t number_o
               (void) hipStreamSynchronize(cur.stream);
             cur.release();
           }
-        if (status != MH_OK)
-          {
-            std::lock_guard<std::mutex> lock(error_lock);
-            if (first_status == MH_OK)
-              {
-                first_status=status;
-                first_error=MhGetLastError();
-              }
-          }
-        else
+        first.record(status);
+        if (status == MH_OK)
           counts[(size_t) logical]++;
       }
     for (const auto &entry : pending)
       {
         DeviceGuard home;
-        MhStatus status=MH_OK;
         if ((home.enter(entry.first) != hipSuccess) || (hipStreamSynchronize(entry.second) != hipSuccess))
-          status=fail(MH_DEVICE_ERROR,"BatchImages: a stream of device %d failed",entry.first);
-        if (status != MH_OK)
-          {
-            std::lock_guard<std::mutex> lock(error_lock);
-            if (first_status == MH_OK)
-              {
-                first_status=status;
-                first_error=MhGetLastError();
-              }
-          }
+          first.record(fail(MH_DEVICE_ERROR,"BatchImages: a stream of device %d failed",entry.first));
       }
   };
-  std::vector<std::thread> pool;
-  for (size_t w=1; w < workers; w++)
-    pool.emplace_back(work,w);
-  work(0);
-  for (std::thread &t : pool)
-    t.join();
+  run_workers(workers,work);
   if (report != nullptr)
     {
       memset(report,0,sizeof(*report));
@@ -882,9 +874,7 @@ MH_API MhStatus MagickHipBatchImages(const MhOperator *operators,size_t number_o
         report->images_per_device[d]=counts[(size_t) d];
       report->seconds=std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
     }
-  if (first_status != MH_OK)
-    return fail(first_status,"%s",first_error.c_str());
-  return MH_OK;
+  return first.result();
 }
 
 MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_operators,
@@ -904,17 +894,8 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
   size_t reach=0;
   for (const PreparedOperator &p : chain)
     {
-      if (changes_geometry(p.op.kind))
-        return fail(MH_UNSUPPORTED,"ShardedImage: resize, sample, scale and thumbnail change the geometry");
-      if (p.op.kind == MH_OP_CLAHE)
-        return fail(MH_UNSUPPORTED,"ShardedImage: CLAHEImage's tile grid belongs to the whole frame");
-      if ((p.op.kind == MH_OP_THRESHOLD) || (p.op.kind == MH_OP_AUTO_THRESHOLD) ||
-          (p.op.kind == MH_OP_ADAPTIVE_THRESHOLD))
-        return fail(MH_UNSUPPORTED,"ShardedImage: the threshold operators are not sharded (AutoThresholdImage needs the "
-          "bands' counts all-reduced, AdaptiveThresholdImage a halo)");
-      if ((p.op.kind == MH_OP_AUTO_LEVEL) || (p.op.kind == MH_OP_LINEAR_STRETCH) || (p.op.kind == MH_OP_NORMALIZE))
-        return fail(MH_UNSUPPORTED,"ShardedImage: AutoLevelImage, LinearStretchImage and NormalizeImage are not sharded "
-          "(the bands' range or counts would have to be all-reduced)");
+      if (p.row->declined != nullptr)
+        return fail(MH_UNSUPPORTED,"%s",p.row->declined);
       if (p.reach == (size_t) -1)
         return fail(MH_UNSUPPORTED,"ShardedImage: iterate-until-convergence has no halo bound");
       reach=p.reach > reach ? p.reach : reach;
@@ -925,8 +906,7 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
   while ((devices > 1) && (H/(size_t) devices < (reach > 0 ? reach : 1)))
     devices--;
   const int physical=device_count();
-  const size_t row_bytes=image->columns*(size_t) image->number_channels*
-    (image->quantum == MH_QUANTUM_U16 ? 2u : 4u);
+  const size_t row_bytes=mh::row_bytes(*image);
 
   struct Band
   {
@@ -935,6 +915,11 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
     size_t y0=0,y1=0,top=0,bottom=0;        // owned rows [y0,y1), halo rows above / below
     Working cur;
     hipEvent_t done=nullptr;                // the band's last operator has been enqueued up to here
+  };
+  // `rows` rows of the frame's layout at `pixels`, on a band's device and stream
+  auto band_view=[image](void *pixels,size_t rows,int device,hipStream_t stream)
+  {
+    return View{pixels,image->columns,rows,(int) image->number_channels,(MhQuantumKind) image->quantum,device,stream};
   };
   std::vector<Band> bands((size_t) devices);
   MhStatus status=MH_OK;
@@ -947,8 +932,9 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
       band.stream=batch_stream(band.device,64+b);
       band.y0=H*(size_t) b/(size_t) devices;
       band.y1=H*(size_t) (b+1)/(size_t) devices;
-      band.top=band.y0 < reach ? band.y0 : reach;
-      band.bottom=H-band.y1 < reach ? H-band.y1 : reach;
+      const BandSlice slice=band_slice(*image,band.y0,band.y1,reach);
+      band.top=slice.top;
+      band.bottom=slice.bottom;
       DeviceGuard guard;
       if ((band.stream == nullptr) || (guard.enter(band.device) != hipSuccess) ||
           (hipEventCreateWithFlags(&band.done,hipEventDisableTiming) != hipSuccess))
@@ -957,16 +943,13 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
           break;
         }
       // the band and its halo rows straight from the source: the first stencil needs no exchange
-      MhImage slice=*image;
-      slice.rows=band.y1-band.y0+band.top+band.bottom;
-      slice.pixels=static_cast<char *>(image->pixels)+(band.y0-band.top)*row_bytes;
-      status=working_copy(slice,band.device,band.stream,band.cur);
+      status=working_copy(slice.image,band.device,band.stream,band.cur);
     }
   bool halos_valid=true;
   for (size_t k=0; (status == MH_OK) && (k < chain.size()); k++)
     {
       const PreparedOperator &p=chain[k];
-      if (p.stencil && !halos_valid && (devices > 1))
+      if (p.row->stencil() && !halos_valid && (devices > 1))
         {
           // every band fetches its neighbours' current edge rows (their owned rows next to the
           // cut) into its halo rows, behind the neighbours' last operator
@@ -1014,12 +997,11 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
         }
       if (status != MH_OK)
         break;
-      if (p.histogram && (devices > 1))
+      if (p.row->histogram && (devices > 1))
         {
           // local tables over the OWNED rows, one all-reduce, identical LUT, local apply
           const bool equalize=p.op.kind == MH_OP_EQUALIZE;
-          const size_t channels=image->number_channels;
-          const size_t count=(size_t) MH_HISTOGRAM_BINS*channels;
+          const size_t count=(size_t) MH_HISTOGRAM_BINS*image->number_channels;
           std::vector<Temp> tables((size_t) devices),flags((size_t) devices);
           std::vector<TableView> views;
           const MhImage &described=bands[0].cur.image;
@@ -1038,14 +1020,8 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
                 break;
               if (hipMemsetAsync(tables[(size_t) b].ptr,0,count*sizeof(unsigned long long),band.stream) != hipSuccess)
                 status=fail(MH_DEVICE_ERROR,"ShardedImage: memset failed");
-              View owned;
-              owned.pixels=static_cast<char *>(band.cur.image.pixels)+band.top*row_bytes;
-              owned.columns=image->columns;
-              owned.rows=band.y1-band.y0;
-              owned.channels=(int) channels;
-              owned.quantum=(MhQuantumKind) image->quantum;
-              owned.device=band.device;
-              owned.stream=band.stream;
+              const View owned=band_view(static_cast<char *>(band.cur.image.pixels)+band.top*row_bytes,
+                band.y1-band.y0,band.device,band.stream);
               if (status == MH_OK)
                 status=launch_histogram(owned,mode,&band.cur.image,tables[(size_t) b].as<unsigned long long>());
               if ((status == MH_OK) && scan)
@@ -1085,14 +1061,7 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
               Band &band=bands[(size_t) b];
               DeviceGuard guard;
               (void) guard.enter(band.device);
-              View whole;
-              whole.pixels=band.cur.image.pixels;
-              whole.columns=image->columns;
-              whole.rows=band.cur.image.rows;
-              whole.channels=(int) channels;
-              whole.quantum=(MhQuantumKind) image->quantum;
-              whole.device=band.device;
-              whole.stream=band.stream;
+              const View whole=band_view(band.cur.image.pixels,band.cur.image.rows,band.device,band.stream);
               // the LUT builders take the WHOLE image's pixel count (enhance.c:1674)
               MhImage full=band.cur.image;
               full.rows=H;
@@ -1109,7 +1078,7 @@ MH_API MhStatus MagickHipShardedImage(const MhOperator *operators,size_t number_
           (void) guard.enter(bands[(size_t) b].device);
           status=apply_operator(p,bands[(size_t) b].cur);
         }
-      if (p.stencil)
+      if (p.row->stencil())
         halos_valid=false;
     }
   // the owned rows of every band, into the caller's image

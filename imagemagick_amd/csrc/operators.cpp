@@ -964,6 +964,12 @@ static MhStatus morphology_apply(const View &src,const View &dst,const MhImage *
   return MH_OK;
 }
 
+// what host_banded_operator takes: an operator without a kernel string
+static MhOperator banded_operator(MhOperatorKind kind,double a0,double a1,double a2,double a3)
+{
+  return MhOperator{(uint32_t) kind,{a0,a1,a2,a3},nullptr};
+}
+
 } // namespace mh
 
 using namespace mh;
@@ -987,13 +993,7 @@ MH_API MhStatus MagickHipMorphologyImageCompose(const MhImage *image,MhImage *mo
   if (compose == MH_MORPHOLOGY_COMPOSE_DEFAULT)
   {
     // host memory: row bands through a pipeline of uploads, kernels and downloads (batch.cpp)
-    MhOperator op;
-    op.kind=MH_OP_MORPHOLOGY;
-    op.args[0]=(double) method;
-    op.args[1]=(double) iterations;
-    op.args[2]=bias;
-    op.args[3]=0.0;
-    op.text=nullptr;
+    const MhOperator op=banded_operator(MH_OP_MORPHOLOGY,(double) method,(double) iterations,bias,0.0);
     bool handled=false;
     MH_TRY(host_banded_operator(op,kernel,image,morphology_image,&handled));
     if (handled)
@@ -1397,13 +1397,7 @@ MH_API MhStatus MagickHipUnsharpMaskImage(const MhImage *image,MhImage *unsharp_
   MH_TRY(gate_pair(image,unsharp_image,"UnsharpMaskImage",true));
   {
     // host memory: row bands through a pipeline of uploads, kernels and downloads (batch.cpp)
-    MhOperator op;
-    op.kind=MH_OP_UNSHARP_MASK;
-    op.args[0]=radius;
-    op.args[1]=sigma;
-    op.args[2]=gain;
-    op.args[3]=threshold;
-    op.text=nullptr;
+    const MhOperator op=banded_operator(MH_OP_UNSHARP_MASK,radius,sigma,gain,threshold);
     bool handled=false;
     MH_TRY(host_banded_operator(op,nullptr,image,unsharp_image,&handled));
     if (handled)

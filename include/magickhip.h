@@ -927,13 +927,19 @@ MH_API MhStatus MagickHipIsImageGray(const MhImage *image,int *is_gray);
   number_devices <= 0 means MhDeviceCount().  More logical devices than physical ones are
   mapped round-robin (logical d runs on physical d mod MhDeviceCount()): that is how the test
   suite rehearses both entry points on a single GPU.
+
+  What the two entry points do with each operator kind is one row of a table in batch.cpp (DESIGN.md
+  section 5): whether the kind works in place, makes a new image of the same geometry or one of
+  args[0] x args[1] (resize, sample, scale, thumbnail: the chain needs result descriptors), how many
+  rows a stencil reaches, and whether MagickHipShardedImage runs it or returns MH_UNSUPPORTED, with
+  the reason in MhGetLastError().
 */
 typedef enum
 {
   MH_OP_BLUR = 1,              /* args: radius, sigma */
   MH_OP_GAUSSIAN_BLUR = 2,     /* args: radius, sigma */
   MH_OP_UNSHARP_MASK = 3,      /* args: radius, sigma, gain, threshold */
-  MH_OP_RESIZE = 4,            /* args: columns, rows, MhFilterType        (batch only) */
+  MH_OP_RESIZE = 4,            /* args: columns, rows, MhFilterType */
   MH_OP_MORPHOLOGY = 5,        /* args: MhMorphologyMethod, iterations, bias; text: kernel string */
   MH_OP_COLORSPACE = 6,        /* args: MhColorspace */
   MH_OP_CONTRAST_STRETCH = 7,  /* args: black_point, white_point (pixel counts, enhance.c:1544) */
@@ -942,28 +948,21 @@ typedef enum
   MH_OP_BILATERAL_BLUR = 10,   /* args: width, height, intensity_sigma, spatial_sigma */
   MH_OP_SELECTIVE_BLUR = 11,   /* args: radius, sigma, threshold */
   MH_OP_KUWAHARA = 12,         /* args: radius, sigma */
-  MH_OP_CLAHE = 13,            /* args: width, height, number_bins, clip_limit; MagickHipBatchImages
-                                  only: MagickHipShardedImage returns MH_UNSUPPORTED for it, the
-                                  tile grid belongs to the whole frame, not to a row band */
+  MH_OP_CLAHE = 13,            /* args: width, height, number_bins, clip_limit */
   MH_OP_THRESHOLD = 14,        /* args: threshold (BilevelImage) */
   MH_OP_AUTO_THRESHOLD = 15,   /* args: MhAutoThresholdMethod */
-  MH_OP_ADAPTIVE_THRESHOLD = 16, /* args: width, height, bias.  These three: MagickHipBatchImages only;
-                                  MagickHipShardedImage returns MH_UNSUPPORTED (AutoThresholdImage would
-                                  need the bands' counts all-reduced, AdaptiveThresholdImage a halo) */
+  MH_OP_ADAPTIVE_THRESHOLD = 16, /* args: width, height, bias */
   MH_OP_LEVEL = 17,            /* args: black_point, white_point, gamma */
   MH_OP_LEVELIZE = 18,         /* args: black_point, white_point, gamma */
   MH_OP_GAMMA = 19,            /* args: gamma */
   MH_OP_NEGATE = 20,           /* args: grayscale */
-  MH_OP_SIGMOIDAL_CONTRAST = 21, /* args: sharpen, contrast, midpoint.  These five are pointwise:
-                                  MagickHipShardedImage runs them band by band, no halo, no collective */
+  MH_OP_SIGMOIDAL_CONTRAST = 21, /* args: sharpen, contrast, midpoint */
   MH_OP_AUTO_LEVEL = 22,
   MH_OP_LINEAR_STRETCH = 23,   /* args: black_point, white_point (pixel counts) */
-  MH_OP_NORMALIZE = 24,        /* These three: MagickHipBatchImages only; MagickHipShardedImage returns
-                                  MH_UNSUPPORTED (the bands' range or counts would have to be all-reduced) */
+  MH_OP_NORMALIZE = 24,
   MH_OP_SAMPLE = 25,           /* args: columns, rows (default sample:offset) */
   MH_OP_SCALE = 26,            /* args: columns, rows */
-  MH_OP_THUMBNAIL = 27         /* args: columns, rows, MhFilterType.  These three change the geometry like
-                                  MH_OP_RESIZE: batch only, and the chain needs result descriptors */
+  MH_OP_THUMBNAIL = 27         /* args: columns, rows, MhFilterType */
 } MhOperatorKind;
 
 typedef struct MhOperator

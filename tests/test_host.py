@@ -48,6 +48,18 @@ def test_no_torch_or_cxx_types_in_the_abi():
     assert "torch" not in text and "std::" not in text and "hipStream_t" not in text
 
 
+def test_binding_names_every_operator_kind_of_the_header():
+    """Every `MH_OP_<NAME> = <n>` of include/magickhip.h is `<name without underscores, lower case>: <n>` in
+    the binding's OPERATORS, and OPERATORS holds nothing else: the part of keeping the kinds in one place
+    that the library's own build-time check of its operator table cannot see."""
+    from imagemagick_amd import _lib
+    text = open(os.path.join(ROOT, "include", "magickhip.h")).read()
+    declared = {name.replace("_", "").lower(): int(value)
+                for name, value in re.findall(r"\bMH_OP_(\w+)\s*=\s*(\d+)", text)}
+    assert len(declared) >= 27 and sorted(declared.values()) == list(range(1, len(declared) + 1))
+    assert _lib.OPERATORS == declared
+
+
 def test_operators_fail_loudly_without_a_device(im):
     if gpu_available():
         pytest.skip("a GPU is present")
