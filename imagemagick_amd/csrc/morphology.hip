@@ -28,6 +28,8 @@
 
 namespace mh {
 
+#include "pixel_intensity.inc.hpp"
+
 struct Cell
 {
   int dx,dy;       // offset of the sample inside the LDS tile, relative to the output pixel's tile position
@@ -50,6 +52,7 @@ struct Morph2DArgs
   uint32_t copy_mask;
   int hmt_mode;              // 0 HitAndMiss, 1 Thinning, 2 Thicken
   int linear,nonlinear,gray,intensity_method;
+  int needs_gamma;           // the intensity method encodes / decodes the samples of this colourspace first
   unsigned long long *changed;
   const unsigned *only_if;   // nullptr, or: leave at once when the word is zero
 };
@@ -58,14 +61,24 @@ constexpr int kTW=64;
 constexpr int kTH=16;
 constexpr int kRowsPerLane=4;
 
-// Rec709Luma etc. for the *Intensity methods.  Only the gamma-free methods
-// are evaluated here; others are rejected by the launcher.
+// GetPixelIntensity for the *Intensity methods (pixel_intensity.inc.hpp).  The methods that need no gamma step
+// are evaluated in line; a frame whose colourspace makes the method encode or decode its samples first (Rec709Luma
+// of linear RGB, the Luminance methods of sRGB: pixel.c:2418-2452) goes through the whole switch behind a call.
 template<typename Q,int C>
 static __device__ __forceinline__ double morph_intensity(const Q (&q)[C],const Morph2DArgs &a)
 {
   double red=(double) q[0];
   if (C == 1)
     return red;
+  if (a.needs_gamma)
+    {
+      IntensityParams ip;
+      ip.method=a.intensity_method;
+      ip.linear=a.linear;
+      ip.nonlinear=a.nonlinear;
+      ip.gray=a.gray;
+      return pixel_intensity_call<Q,C>(q,ip);
+    }
   double green=(double) q[(C >= 3) && !a.gray ? 1 : 0];
   double blue=(double) q[(C >= 3) && !a.gray ? 2 : 0];
   switch (a.intensity_method)
@@ -86,7 +99,8 @@ static __device__ __forceinline__ double morph_intensity(const Q (&q)[C],const M
     }
     case MH_INTENSITY_MS: return (red*red+green*green+blue*blue)/(3.0*kQR);
     case MH_INTENSITY_RMS: return sqrt(red*red+green*green+blue*blue)/sqrt(3.0);
-    case MH_INTENSITY_REC601LUMA: return 0.298839*red+0.586811*green+0.114350*blue;
+    case MH_INTENSITY_REC601LUMA: case MH_INTENSITY_REC601LUMINANCE:
+      return 0.298839*red+0.586811*green+0.114350*blue;
     default: break;
   }
   return 0.212656*red+0.715158*green+0.072186*blue;
@@ -1753,20 +1767,15 @@ MhStatus launch_morph2d(const View &src,const View &dst,const Morph2DParams &par
     (params.colorspace == MH_COLORSPACE_LINEARGRAY);
   const bool nonlinear=(params.colorspace == MH_COLORSPACE_SRGB) ||
     (params.colorspace == MH_COLORSPACE_GRAY);
+  bool needs_gamma=false;
   if ((mc == MC_ERODE_INTENSITY) || (mc == MC_DILATE_INTENSITY))
+    switch (params.intensity)
     {
-      // the gamma-dependent intensity methods are not evaluated in this kernel
-      bool needs_gamma=false;
-      switch (params.intensity)
-      {
-        case MH_INTENSITY_REC601LUMA: case MH_INTENSITY_REC709LUMA: case MH_INTENSITY_UNDEFINED:
-          needs_gamma=linear; break;
-        case MH_INTENSITY_REC601LUMINANCE: case MH_INTENSITY_REC709LUMINANCE:
-          needs_gamma=true; break;
-        default: break;
-      }
-      if (needs_gamma)
-        return fail(MH_UNSUPPORTED,"intensity method needs a gamma transform");
+      case MH_INTENSITY_REC601LUMA: case MH_INTENSITY_REC709LUMA: case MH_INTENSITY_UNDEFINED:
+        needs_gamma=linear; break;
+      case MH_INTENSITY_REC601LUMINANCE: case MH_INTENSITY_REC709LUMINANCE:
+        needs_gamma=nonlinear; break;
+      default: break;
     }
   // origin offsets, morphology.c:2623-2637
   const int ox=reflected ? w-(int) k->x-1 : (int) k->x;
@@ -1827,6 +1836,7 @@ MhStatus launch_morph2d(const View &src,const View &dst,const Morph2DParams &par
   args.gray=(params.colorspace == MH_COLORSPACE_GRAY) ||
     (params.colorspace == MH_COLORSPACE_LINEARGRAY) || (src.channels < 3);
   args.intensity_method=(int) params.intensity;
+  args.needs_gamma=needs_gamma ? 1 : 0;
   args.changed=changed;
   Temp d_cells;
   Cell dummy{0,0,0.0};

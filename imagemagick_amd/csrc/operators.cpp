@@ -308,6 +308,14 @@ static MhStatus separable_convolve(const View &src,const View &dst,const MhKerne
   return MH_OK;
 }
 
+// GetImageChannels (image-private.h:147-164): what MorphologyPrimitive divides its count of changed samples by
+// (morphology.c:2806, :3226) — the channels that carry the update trait, not the pixel's width
+static unsigned long long counted_channels(const Roles &roles)
+{
+  const int n=__builtin_popcount(roles.update_mask);
+  return n == 0 ? 1ull : (unsigned long long) n;
+}
+
 // One MorphologyPrimitive(curr -> work), morphology.c:2566.  `changed`
 // (optional, device counter, must be zero on entry) accumulates the number of
 // changed channel values.
@@ -340,9 +348,11 @@ static MhStatus primitive(const View &src,const View &dst,MhMorphologyMethod met
   // channels of a frame a quarter as tall (gray_bands_pack_kernel, pointwise.hip; the kernel's reach in extra rows
   // between bands), so that the wide-pixel kernels below take it — the matrix-core forms, the separated passes.
   // Every channel of a frame without alpha weighting is summed on its own (morphology.c:2892-2979): the result is
-  // the frame's own under the same contract.
-  if ((method == MH_MORPHOLOGY_CONVOLVE) && (src.quantum == MH_QUANTUM_U16) && (src.channels == 1) &&
-      !roles.blend && (roles.copy_mask == 0) && (kernel->width >= 2) && (kernel->height >= 2) &&
+  // the frame's own under the same contract.  Not with a change count: that compares the UNROUNDED sum with the
+  // source sample (morphology.c:3199), and the bands come back as levels (an identity kernel with a bias of 0.25
+  // changes every sample and no level) — the generic kernel counts, like behind every other fast Convolve route.
+  if ((method == MH_MORPHOLOGY_CONVOLVE) && (changed == nullptr) && (src.quantum == MH_QUANTUM_U16) &&
+      (src.channels == 1) && !roles.blend && (roles.copy_mask == 0) && (kernel->width >= 2) && (kernel->height >= 2) &&
       (option("MAGICKHIP_NO_GRAY_BANDS") == nullptr))
     {
       const int above=(int) kernel->y,below=(int) kernel->height-1-(int) kernel->y;
@@ -352,7 +362,7 @@ static MhStatus primitive(const View &src,const View &dst,MhMorphologyMethod met
           GrayBands bands;
           MH_TRY(bands.pack(src,halo));
           MH_TRY(primitive(bands.packed,bands.result,method,kernel,bias,GrayBands::plain_roles(),desc,nullptr,mode));
-          return bands.unpack(dst,src.pixels,changed);
+          return bands.unpack(dst);
         }
     }
   if ((method == MH_MORPHOLOGY_CONVOLVE) && (changed == nullptr) && (bias == 0.0) &&
@@ -907,8 +917,8 @@ static MhStatus morphology_apply(const View &src,const View &dst,const MhImage *
                       MH_HIP(hipMemcpyAsync(&host,changed_dev,sizeof(host),
                         hipMemcpyDeviceToHost,src.stream));
                       MH_HIP(hipStreamSynchronize(src.stream));
-                      // changed/GetImageChannels(image), morphology.c:2806, :3225
-                      changed=(ptrdiff_t) (host/(unsigned long long) src.channels);
+                      // changed/GetImageChannels(image), morphology.c:2806, :3226
+                      changed=(ptrdiff_t) (host/counted_channels(roles));
                     }
                   else
                     changed=1;
@@ -1038,7 +1048,7 @@ MH_API MhStatus MagickHipMorphologyPrimitive(const MhImage *image,MhImage *morph
     pair.src.view.stream));
   MH_HIP(hipStreamSynchronize(pair.src.view.stream));
   if (changed != nullptr)
-    *changed=(ptrdiff_t) (host/(unsigned long long) image->number_channels);
+    *changed=(ptrdiff_t) (host/counted_channels(roles));
   return pair.commit();
 }
 
