@@ -1613,7 +1613,7 @@ static MhStatus launch_tri_waves(const View &src,const View &dst,bool vertical,
       size_t table_bytes=A::taps_in_lds ? (((size_t) K*sizeof(T)+15u) & ~(size_t) 15u) : 0;
       size_t lds_tile=table_bytes+(size_t) (WAVES*R+K-1)*64*C*sizeof(Q);
       ProfileScope prof("conv_column",src.stream);
-      if ((lds_tile <= 80u*1024u) && (option("MAGICKHIP_NO_COLUMN_LDS") == nullptr))
+      if (lds_tile <= 80u*1024u)
         {
           if (lds_tile > 64u*1024u)
             MH_HIP(hipFuncSetAttribute(
@@ -2131,20 +2131,20 @@ static MhStatus launch_folded(const View &src,const SeparableArgs &sep,const Con
   // (measured on 4096^2, tools/time_fold_variants.py: the column pass of a short kernel is faster with four
   // outputs a lane — 106 registers, four waves a SIMD — than with eight: 0.19 / 0.22 / 0.25 ms against
   // 0.24 / 0.28 / 0.28 for 7 / 13 / 19 taps; from 25 taps on the fewer re-read rows of eight win)
-  const int r8_rows=(int) option_long("MAGICKHIP_FOLD_R8_ROW_MIN",9),r8_columns=(int) option_long("MAGICKHIP_FOLD_R8_COLUMN_MIN",25);
+  constexpr int r8_rows=9,r8_columns=25;
   // (samples in flight: four instead of eight where that buys a wave more per SIMD — the float
   // frame's row pass, 194 -> ~140 registers, and every column pass, whose samples are doubles: the
   // fp64 pipe sustains more with more waves, tools/ubench/fma_f64_rate.hip.  0x10 on 8192^2: column
   // 1.44 -> 1.28 ms, float row 1.24 -> 1.14.)
-  if ((horizontal.ntaps >= (r8_rows < 9 ? 9 : r8_rows)) && QuantumOps<Q>::is_float)
+  if ((horizontal.ntaps >= r8_rows) && QuantumOps<Q>::is_float)
     MH_TRY((launch_folded_row<Q,C,BLEND,8,4>(src,sep,horizontal)));
-  else if (horizontal.ntaps >= (r8_rows < 9 ? 9 : r8_rows))
+  else if (horizontal.ntaps >= r8_rows)
     MH_TRY((launch_folded_row<Q,C,BLEND,8,8>(src,sep,horizontal)));
   else if (horizontal.ntaps >= 5)
     MH_TRY((launch_folded_row<Q,C,BLEND,4,4>(src,sep,horizontal)));
   else
     MH_TRY((launch_folded_row<Q,C,BLEND,2,2>(src,sep,horizontal)));
-  if (vertical.ntaps >= (r8_columns < 9 ? 9 : r8_columns))
+  if (vertical.ntaps >= r8_columns)
     MH_TRY((launch_folded_column<Q,C,BLEND,8,4>(src,sep,vertical)));
   else if (vertical.ntaps >= 5)
     MH_TRY((launch_folded_column<Q,C,BLEND,4,4>(src,sep,vertical)));
@@ -2325,7 +2325,6 @@ MhStatus launch_conv1d_column_unsharp(const View &rows,const View &dst,const Vie
   if ((!is_float && (prec != MH_PRECISION_EXACT)) || (params.ntaps < 16) || (params.bias != 0.0) ||
       (original.columns != rows.columns) || (original.rows != rows.rows) ||
       (original.channels != rows.channels) || (original.quantum != rows.quantum) ||
-      (option("MAGICKHIP_NO_TRI") != nullptr) || (option("MAGICKHIP_NO_TIE64") != nullptr) ||
       (option("MAGICKHIP_NO_FUSED_UNSHARP") != nullptr))
     return MH_OK;
   double total=0.0;
@@ -2354,7 +2353,7 @@ MhStatus launch_conv1d_sums64(const View &src,const View &dst,bool vertical,cons
 {
   Roles plain;
   plain.update_mask=0xfu;
-  if ((params.ntaps >= 16) && (option("MAGICKHIP_NO_TRI") == nullptr))
+  if (params.ntaps >= 16)
     return launch_tri<double,4,false,Fma64,8,8>(src,dst,vertical,params,plain,nullptr);
   return launch_one<double,4,false,Fma64,8>(src,dst,vertical,params,plain,nullptr);
 }
@@ -2472,7 +2471,7 @@ MhStatus launch_conv1d(const View &src,const View &dst,bool vertical,
           // long kernels: the triangular kernels with 32 outputs per lane; short ones: blocked
           // K >= R+1: the ramp-free triangular kernels (measured +7.5 % at K=79 on MI355X;
           // R=24/32 variants were slower: 240 VGPRs leave two waves per SIMD)
-          if ((params.ntaps >= 24) && (option("MAGICKHIP_NO_TRI") == nullptr))
+          if (params.ntaps >= 24)
             MH_TRY((dispatch_tri<Fast32,16,4>(src,dst,vertical,params,roles,changed)));
           else
             MH_TRY((dispatch_blocked<Fast32,16,4>(src,dst,vertical,params,roles,changed)));
@@ -2482,7 +2481,7 @@ MhStatus launch_conv1d(const View &src,const View &dst,bool vertical,
             MH_TRY(launch_row_alpha_audit(src,dst,params));
           return MH_OK;
         }
-      if ((params.ntaps >= 16) && (option("MAGICKHIP_NO_TRI") == nullptr))
+      if (params.ntaps >= 16)
         {
           // fused sums + reference-order recomputation of the results they cannot decide: the
           // same bits at less than half the fp64 work (device_common.hpp, Tie64).  Positive taps
@@ -2491,7 +2490,7 @@ MhStatus launch_conv1d(const View &src,const View &dst,bool vertical,
           bool positive=true;
           for (int v=0; v < params.ntaps; v++)
             positive=positive && (params.taps[v] >= 0.0);
-          if (positive && (params.bias == 0.0) && (changed == nullptr) && (option("MAGICKHIP_NO_TIE64") == nullptr))
+          if (positive && (params.bias == 0.0) && (changed == nullptr))
             return dispatch_tri<Tie64,8,8>(src,dst,vertical,params,roles,changed);
           return dispatch_tri<Exact64,8,8>(src,dst,vertical,params,roles,changed);
         }
@@ -2501,8 +2500,7 @@ MhStatus launch_conv1d(const View &src,const View &dst,bool vertical,
   // within 1 ULP of a float result.  Long normalised positive kernels (BlurImage's) take the
   // fused sums with the float-rounding tie check of Accum::finish(): the same bits as the
   // reference's order at 4 fused multiply-adds per tap instead of 11 separately rounded operations.
-  if ((params.ntaps >= 16) && (params.bias == 0.0) && (changed == nullptr) &&
-      (option("MAGICKHIP_NO_TRI") == nullptr) && (option("MAGICKHIP_NO_TIE64") == nullptr))
+  if ((params.ntaps >= 16) && (params.bias == 0.0) && (changed == nullptr))
     {
       bool positive=true;
       double total=0.0;

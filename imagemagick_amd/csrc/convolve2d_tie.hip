@@ -286,8 +286,7 @@ MhStatus launch_conv2d_tie(const View &src,const View &dst,const MhKernelInfo *k
       (src.channels != dst.channels) || (src.columns != dst.columns) || (src.rows != dst.rows) ||
       (src.pixels == dst.pixels) || (kw < 2) || (kh < 1) || (kw*kh < 25) ||     // kw == 1: see below (kernel->x < 0) || (kernel->y < 0) ||
       (kernel->x >= kw) || (kernel->y >= kh) || (src.columns >= (1u << 30)) ||
-      ((src.rows+kTieH-1)/kTieH > 65535u) ||                 // (gridDim.y)
-      (option("MAGICKHIP_NO_TIE_2D") != nullptr))
+      ((src.rows+kTieH-1)/kTieH > 65535u))                   // (gridDim.y)
     return MH_OK;
   // (a one-column kernel is the reference's width == 1 fast path, morphology.c:2654-2807, which
   // scales gamma by height / count when NaN cells leave fewer than `height` terms — :2775-2776.

@@ -115,19 +115,6 @@ struct HybridGeometry
   static_assert((alpha_bytes % 16) == 0,"aligned planes");
 };
 
-// Diagnostic builds only (-DMH_HYBRID_KNOCK, tools/gpu_hybrid_knock.sh): parts of the alpha path are
-// skipped at run time (bits of MAGICKHIP_HYBRID_KNOCK, handed over in args.threshold) to see what
-// each costs.  The results are wrong.  1 the alpha tiles' digit loads and products, 2 the alpha
-// epilogue of interval A, 4 the colour epilogue's reads of the exact alpha, 8 exact_sums,
-// 16 the staging of the alpha byte planes; 32 / 64 / 128: plain-channel arithmetic in the staging /
-// the colour epilogue / the column pass's epilogue of an alpha-weighted frame; 256: every fetch reads
-// the strip's first group (cache-resident: no memory latency, no read traffic); 512: no stores
-#ifdef MH_HYBRID_KNOCK
-#define MH_HKNOCKED(bit) ((args.threshold & (bit)) != 0)
-#else
-#define MH_HKNOCKED(bit) false
-#endif
-
 // Diagnostic build only (-DMH_HYBRID_TRACE, tools/trace_hybrid_blur.py): every wave of the first four
 // workgroups stamps the shader clock at the phase boundaries of 48 steady-state iterations:
 // trace[block][wave][iteration][mark].
@@ -344,7 +331,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   {
     if (stager)
       {
-        int y=in0+G::GROUP*(MH_HKNOCKED(256) ? 0 : g)+srow;
+        int y=in0+G::GROUP*g+srow;
         y=y < 0 ? 0 : (y > H-1 ? H-1 : y);       // the intermediate's edge clamp (cache.c:2663-2679)
         const int xs=xin0+4*sxg;
         if (__builtin_expect(!edge_item,1))
@@ -394,10 +381,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
     if (stager)
       {
         f32x2 v[4][2];
-        if (MH_HKNOCKED(32))
-          quantum_to_samples<MFMA_PLAIN4>(raw,v);
-        else
-          quantum_to_samples<SAMPLES>(raw,v);
+        quantum_to_samples<SAMPLES>(raw,v);
         // (one address + immediate offsets)
         unsigned char *to=smem_raw+G::ring_bytes+2*(srow*F::SR+4*sxg);
         // (RGB frames: the fourth plane stays as it is — its row tiles are not run, what the column pass makes of it
@@ -413,7 +397,6 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             *reinterpret_cast<uint2 *>(to+2*(G::STAGE_PLANE+c*F::CHR))=lo;
           }
         if constexpr (BLEND)
-          if (!MH_HKNOCKED(16))
           {
             // bytes 2,3 of the second word of each pixel = the alpha level, paired over the four positions
             const unsigned hy01=__builtin_amdgcn_perm(raw[1].y,raw[0].y,0x07030602u),hy23=__builtin_amdgcn_perm(raw[3].y,raw[2].y,0x07030602u);
@@ -500,7 +483,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       {
         const uint2 result=out_tile[wave*G::OUT_STRIDE+lane];
         const int x=x0+lane,y=out_begin+G::GROUP*block+wave;
-        if ((x < W) && (y < H) && !MH_HKNOCKED(512))
+        if ((x < W) && (y < H))
           store_pixel16(args.dst+pixel_index(y,W,x)*PX,result);
       }
   };
@@ -526,7 +509,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       MH_HTRACE_MARK(2);
       // ======================================================================== interval A
       if constexpr (BLEND)
-        if (alpha_wave && !MH_HKNOCKED(2))
+        if (alpha_wave)
           {
             // ---- the exact alpha sums of this wave's 16 x 16 tile of group g-1.  Sample = level*2^16: byte
             // planes 2 (low) and 3 (high); the products b_3 x d_j (class j) and b_2 x d_j (class j-1; b_2 x d_0
@@ -535,37 +518,31 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
 #pragma unroll
             for (int c=0; c < 5; c++)
               tiles[c]=intx4{0,0,0,0};
-            if (!MH_HKNOCKED(1))
+            // five tiles, then four: an instruction's tile was last written five instructions
+            // earlier (a dependent v_mfma waits for its predecessor's passes)
+#pragma unroll
+            for (int j=0; j < kExactDigits; j++)
+              tiles[j]=digit_product(plane_high,operand[j],tiles[j]);
+#pragma unroll
+            for (int j=1; j < kExactDigits; j++)
+              tiles[j-1]=digit_product(plane_low,operand[j],tiles[j-1]);
+            if constexpr (G::NX == 2)
               {
-                // five tiles, then four: an instruction's tile was last written five instructions
-                // earlier (a dependent v_mfma waits for its predecessor's passes)
+                auto join=[](unsigned lo,unsigned hi) { return (long) (((unsigned long) hi << 32) | (unsigned long) lo); };
+                const long digit[kExactDigits]={
+                  join((unsigned) operand[NOPERANDS-1][0],(unsigned) operand[NOPERANDS-1][1]),
+                  join((unsigned) operand[NOPERANDS-1][2],(unsigned) operand[NOPERANDS-1][3]),
+                  join(raw[0].x,raw[0].y),join(raw[1].x,raw[1].y),join(raw[2].x,raw[2].y)};
 #pragma unroll
                 for (int j=0; j < kExactDigits; j++)
-                  tiles[j]=digit_product(plane_high,operand[j],tiles[j]);
+                  tiles[j]=digit_product(plane_high2,digit[j],tiles[j]);
 #pragma unroll
                 for (int j=1; j < kExactDigits; j++)
-                  tiles[j-1]=digit_product(plane_low,operand[j],tiles[j-1]);
-                if constexpr (G::NX == 2)
-                  {
-                    auto join=[](unsigned lo,unsigned hi) { return (long) (((unsigned long) hi << 32) | (unsigned long) lo); };
-                    const long digit[kExactDigits]={
-                      join((unsigned) operand[NOPERANDS-1][0],(unsigned) operand[NOPERANDS-1][1]),
-                      join((unsigned) operand[NOPERANDS-1][2],(unsigned) operand[NOPERANDS-1][3]),
-                      join(raw[0].x,raw[0].y),join(raw[1].x,raw[1].y),join(raw[2].x,raw[2].y)};
-#pragma unroll
-                    for (int j=0; j < kExactDigits; j++)
-                      tiles[j]=digit_product(plane_high2,digit[j],tiles[j]);
-#pragma unroll
-                    for (int j=1; j < kExactDigits; j++)
-                      tiles[j-1]=digit_product(plane_low2,digit[j],tiles[j-1]);
-                  }
+                  tiles[j-1]=digit_product(plane_low2,digit[j],tiles[j-1]);
               }
             // ---- the alpha levels of group g-1 from the class tiles
             double sums_alpha[4];
-            if (!MH_HKNOCKED(8))
-              exact_sums(tiles,args.offset,sums_alpha);
-            else
-              sums_alpha[0]=sums_alpha[1]=sums_alpha[2]=sums_alpha[3]=0.0;
+            exact_sums(tiles,args.offset,sums_alpha);
             unsigned q[4];
             const bool doubtful=exact_levels<false>(sums_alpha,args,q);
             const int x=x0+16*alpha_tile+n;
@@ -646,8 +623,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
               }
 #pragma unroll
             for (int i=0; i < N; i++)
-              out_tile[n*G::OUT_STRIDE+4*(ctile0+done+i)+kq]=MH_HKNOCKED(128) ?
-                sums_to_quantum<MFMA_PLAIN4>(acc[i][0],acc[i][1],acc[i][2],acc[i][3],args.quantum_unit) :
+              out_tile[n*G::OUT_STRIDE+4*(ctile0+done+i)+kq]=
                 sums_to_quantum<SAMPLES>(acc[i][0],acc[i][1],acc[i][2],acc[i][3],args.quantum_unit);
           };
           for (int done=0; done < ctiles; done+=CT)
@@ -670,7 +646,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
         // (at the head of the epilogue's dependent chain it cost 0.04 ms per frame)
         floatx4 weight={1.0f,1.0f,1.0f,1.0f};
         if constexpr (BLEND)
-          if (row_wave && !MH_HKNOCKED(4))
+          if (row_wave)
             weight=*reinterpret_cast<const floatx4 *>(alpha_weight+weight_slot(ot));
         if constexpr (BLEND)
           if (alpha_wave)
@@ -703,7 +679,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
                 acc=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi,toeplitz_lo(c),acc,0,0,0);
               }
             float v[4];
-            if (BLEND && !MH_HKNOCKED(64))
+            if (BLEND)
               {
 #pragma unroll
                 for (int r=0; r < 4; r++)
@@ -882,7 +858,7 @@ MhStatus launch_blur_fused_hybrid(const View &src,const View &dst,const double *
   args.alpha_half_window=0.5-plan.alpha_window_plain;
   args.alpha_floor=plan.alpha_floor;
   args.gain=0.0f;
-  args.threshold=(int) option_long("MAGICKHIP_HYBRID_KNOCK",0);       // diagnostic builds only (MH_HKNOCKED)
+  args.threshold=0;
   args.recomputed=exact_recomputed_counter(src.device);
   args.give_up=nullptr;
   args.trace=nullptr;

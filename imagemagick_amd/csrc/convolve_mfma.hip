@@ -54,7 +54,6 @@ struct ConvMfmaArgs
 {
   const uint16_t *src;
   uint16_t *dst;
-  unsigned long long *trace;   // diagnostic builds only
   const uint16_t *orig;        // MFMA_UNSHARP: the unblurred frame
   float gain;                  // MFMA_UNSHARP
   int threshold;               // MFMA_UNSHARP: ceil(QuantumRange*threshold), see unsharp_pair
@@ -136,22 +135,6 @@ struct MfmaGeometry
 // 4 waves: wave w multiplies unit group w&1 (8 units = 32 entries) by output group w>>1
 // (32 outputs) of the step.
 // MODE: an MfmaMode (mfma_common.hpp).
-
-// Diagnostic build only (-DMH_MFMA_TRACE, tools/trace_blur_steps.py): wave 0 of a few workgroups
-// records the shader clock at the phase boundaries of its first steps.
-#ifdef MH_MFMA_TRACE
-#define MH_TRACE_MARK(id) \
-  do { \
-    if ((trace != nullptr) && (trace_step < 48)) \
-      { \
-        const unsigned long long now=__builtin_readcyclecounter(); \
-        if (lane == 0) \
-          trace[trace_step*8+(id)]=now; \
-      } \
-  } while (0)
-#else
-#define MH_TRACE_MARK(id) do { } while (0)
-#endif
 
 struct __attribute__((packed,aligned(2))) Rgb16 { uint16_t c[3]; };
 
@@ -322,12 +305,6 @@ void conv_mfma_kernel(ConvMfmaArgs args)
   };
 
   const int entry=(n & 3)*G::CH+(8*mg+(n >> 2))*G::S+8*half;    // this lane's operand line
-#ifdef MH_MFMA_TRACE
-  unsigned long long *trace=nullptr;
-  int trace_step=0;
-  if ((args.trace != nullptr) && (wave == 0) && ((blockIdx.x % 97) == 0) && (blockIdx.x/97 < 8))
-    trace=args.trace+(size_t) (blockIdx.x/97)*48*8;
-#endif
   const int items=args.strips*args.segments;
   for (int item=(int) blockIdx.x; item < items; item+=(int) gridDim.x)
     {
@@ -366,7 +343,6 @@ void conv_mfma_kernel(ConvMfmaArgs args)
         {
           const int out0=kStepOutputs*step;
           const bool has_next=step+1 < step_end;
-          MH_TRACE_MARK(0);
           // MFMA_UNSHARP: this step's unblurred pixels were fetched a step ago, together with the
           // samples of the next step; keep them aside, the registers are refilled below
           uint4 mine[kOriginals];
@@ -459,30 +435,16 @@ void conv_mfma_kernel(ConvMfmaArgs args)
                 }
             }
           }
-#ifdef MH_MFMA_TRACE
-          asm volatile("s_nop 0" :: "v"(result[0].x),"v"(result[3].y));      // the epilogue has issued
-#endif
-          MH_TRACE_MARK(1);
           __syncthreads();                       // B2: this step's ring slots may be overwritten
-          MH_TRACE_MARK(2);
           if (has_next)
             {
               int slot=base+4*stage_group;       // positions in0+R+64j+4g -> slots (64j+4g) mod R
               slot=slot >= R ? slot-R : slot;
-#ifdef MH_MFMA_TRACE
-              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-              MH_TRACE_MARK(3);
-#endif
               stage(raw,slot);
-#ifdef MH_MFMA_TRACE
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              MH_TRACE_MARK(4);
-#endif
               if (step+2 < step_end)
                 fetch(raw,unit0,in0+(out0-out_begin)+R+kStepOutputs+4*stage_group);
               fetch_original(unit0,out0+kStepOutputs);
             }
-          MH_TRACE_MARK(5);
           // ---- stores
           if (VERTICAL && (MODE == MFMA_PLAIN3))
             {
@@ -570,12 +532,7 @@ void conv_mfma_kernel(ConvMfmaArgs args)
             }
           base+=kStepOutputs;
           base=base >= R ? base-R : base;
-          MH_TRACE_MARK(6);
           __syncthreads();                       // next step's samples are in the ring; tile_out is free
-          MH_TRACE_MARK(7);
-#ifdef MH_MFMA_TRACE
-          trace_step++;
-#endif
         }
     }
 }
@@ -605,9 +562,7 @@ static MhStatus launch_mfma_typed(const View &src,ConvMfmaArgs &args)
   // three per CU even where four fit (row pass up to 79 taps, both passes up to 33): measured
   // 0.515 / 0.559 ms (3 / 4 per CU, sigma 4) and 0.538 / 0.543 ms (sigma 10) — the passes run
   // against the power limit, more waves in flight only lower the clock
-  int per_cu=resident > 3 ? 3 : resident;
-  if (const char *e=option("MAGICKHIP_MFMA_PER_CU"))
-    per_cu=atoi(e) < 1 ? 1 : (atoi(e) < per_cu ? atoi(e) : per_cu);
+  const int per_cu=resident > 3 ? 3 : resident;
   const int nblocks=compute_units(src.device)*per_cu;
   // Cut the strips into segments so that the work items divide evenly among the resident
   // workgroups.  A segment re-stages R-64 positions, so it stays at least 8 steps long.
@@ -628,37 +583,10 @@ static MhStatus launch_mfma_typed(const View &src,ConvMfmaArgs &args)
     }
   args.segments=segments;
   args.steps_per_segment=(args.steps+segments-1)/segments;
-#ifdef MH_MFMA_TRACE
-  args.trace=nullptr;
-  const char *trace_path=option("MAGICKHIP_MFMA_TRACE");
-  const size_t trace_bytes=8u*48u*8u*sizeof(unsigned long long);
-  if (trace_path != nullptr)
-    {
-      MH_HIP(hipMalloc(reinterpret_cast<void **>(&args.trace),trace_bytes));
-      MH_HIP(hipMemsetAsync(args.trace,0,trace_bytes,src.stream));
-    }
-#else
-  args.trace=nullptr;
-#endif
   ProfileScope prof(VERTICAL ? "conv_column" : "conv_row",src.stream);
   hipLaunchKernelGGL((conv_mfma_kernel<VERTICAL,NQ,MODE,IO>),dim3((unsigned) nblocks),dim3(256),lds,
     src.stream,args);
   MH_HIP(hipGetLastError());
-#ifdef MH_MFMA_TRACE
-  if (args.trace != nullptr)
-    {
-      std::vector<unsigned long long> host(trace_bytes/sizeof(unsigned long long));
-      MH_HIP(hipMemcpyAsync(host.data(),args.trace,trace_bytes,hipMemcpyDeviceToHost,src.stream));
-      MH_HIP(hipStreamSynchronize(src.stream));
-      MH_HIP(hipFree(args.trace));
-      std::string path=std::string(trace_path)+(VERTICAL ? ".column" : ".row");
-      if (FILE *f=fopen(path.c_str(),"wb"))
-        {
-          fwrite(host.data(),1,trace_bytes,f);
-          fclose(f);
-        }
-    }
-#endif
   return MH_OK;
 }
 

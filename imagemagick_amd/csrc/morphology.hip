@@ -762,7 +762,7 @@ void morph_rects_kernel(RectsArgs args)
       }
     const unsigned row_bytes=(unsigned) W*(unsigned) PXB;
     const unsigned char *base=reinterpret_cast<const unsigned char *>(args.src);
-    constexpr int BATCH=NWAVES >= 16 ? 5 : (NWAVES >= 12 ? 4 : 7);  // Disk:15: 13 (6 waves) or 7 (12 waves) rows per thread, two round trips
+    constexpr int BATCH=4;                       // Disk:15: 7 rows per thread (12 waves), two round trips
     for (int q0=wave; q0 < tile_rows; q0+=NWAVES*BATCH)
       {
         Group g[BATCH];
@@ -1018,404 +1018,13 @@ static MhStatus launch_rects_typed(const RectsArgs &args,size_t lds,hipStream_t 
   return MH_OK;
 }
 
-// shape: 0 = 6 waves x 8 rows, 1 = 12 waves x 4 rows, 3 = 16 waves x 3 rows (48 output rows
-// each), 2 = 12 waves x 8 rows (Q16; float Quantum runs shape 1)
+// 12 waves x 4 rows: kRectsRows output rows a workgroup
+constexpr int kRectsRows=48;
+
 template<typename Q,int C>
-static MhStatus launch_rects(bool dilate,int shape,const RectsArgs &args,size_t lds,hipStream_t stream)
+static MhStatus launch_rects(bool dilate,const RectsArgs &args,size_t lds,hipStream_t stream)
 {
-  if constexpr (sizeof(Q) == 2)
-    {
-      if (shape == 3)
-        return dilate ? launch_rects_typed<Q,C,true,3,16>(args,lds,stream) : launch_rects_typed<Q,C,false,3,16>(args,lds,stream);
-      if (shape == 2)
-        return dilate ? launch_rects_typed<Q,C,true,8,12>(args,lds,stream) : launch_rects_typed<Q,C,false,8,12>(args,lds,stream);
-      if (shape == 0)
-        return dilate ? launch_rects_typed<Q,C,true,8,6>(args,lds,stream) : launch_rects_typed<Q,C,false,8,6>(args,lds,stream);
-    }
   return dilate ? launch_rects_typed<Q,C,true,4,12>(args,lds,stream) : launch_rects_typed<Q,C,false,4,12>(args,lds,stream);
-}
-
-// ------------------------------------------------ the same evaluation as a walk down a strip
-// morph_rects_kernel spends a third of its vector instructions on columns it discards (a wave of
-// 128 columns keeps 128-2*hmax) and on the v_mov_dpp that fetch a neighbour lane's edge column, it
-// reads every staged row 2*SY times per output row quad, and it stages TH+2*vmax rows for TH rows
-// of output.  This kernel
-//   * gives a lane FOUR adjacent columns: a wave = 256 columns, 256-2*hmax kept; Row(1) costs 6
-//     packed min/max + 2 cross-lane moves per word plane instead of 8 + 4 for the same four
-//     columns (the pair maxima (a,b) and (c,d) are shared by the columns next to them);
-//   * lets a wave slide over its rows: output rows c and c+1 at fold depth k need rows c-k, c+k and
-//     c+1-k, c+1+k — two of the four were loaded for depth k-1, so a depth costs two row reads;
-//   * lets a workgroup walk DOWN its strip through a ring of 2*TH+2*vmax rows in LDS: the rows two
-//     successive tiles share stay where they are, and the TH new rows of the next tile are written
-//     by global_load_lds_dwordx4 (memory -> LDS without passing through registers) while this tile
-//     is evaluated.  Every source row is read once per strip: the frame is read 256/(256-2*hmax)
-//     times instead of (128/(128-2*hmax))*(TH+2*vmax)/TH.
-// One workgroup per CU (a ring row is 2 KiB for RGBA), one barrier per tile.
-struct StripsArgs
-{
-  RectsArgs r;                // tiles_x = strips, tiles_y = ceil(rows/TH): steps of a whole strip
-  int segments;               // vertical cuts of a strip: work items = strips*segments
-  int steps_per_segment;
-  int items_per_xcd;
-};
-
-template<int C,bool DILATE,int NWAVES>
-__global__ __launch_bounds__(64*NWAVES)
-void morph_strips_kernel(StripsArgs sargs)
-{
-  static_assert((C == 2) || (C == 4),"whole 32-bit words per pixel");
-  const RectsArgs &args=sargs.r;
-  constexpr int SX=4;                          // columns per lane
-  constexpr int SY=2;                          // rows per wave
-  constexpr int NW=C/2;                        // 32-bit words per pixel
-  constexpr int WPR=SX*NW;                     // words a lane holds per row
-  constexpr int HW=WPR/2;                      // ... per half (two columns): one LDS access
-  constexpr int TH=SY*NWAVES;                  // output rows per step
-  constexpr int kStoreDepth=4;                 // 1 + a multiple of 3
-  typedef uint32_t Half __attribute__((ext_vector_type(HW)));
-  typedef Half __attribute__((aligned(4))) LooseHalf;        // global memory: pixel alignment only
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  Half *ring=reinterpret_cast<Half *>(smem_raw);             // [2*TH+2*vmax][2 halves][64 lanes]
-  const int W=args.columns,H=args.rows;
-  const int hmax=args.hmax,vmax=args.vmax,halo=2*vmax;
-  const int R=2*TH+halo;                       // ring rows
-  const int tid=(int) threadIdx.x,lane=tid & 63;
-  const int wave=__builtin_amdgcn_readfirstlane(tid >> 6);
-  const int item=((int) blockIdx.x & 7)*sargs.items_per_xcd+((int) blockIdx.x >> 3);
-  if (item >= args.tiles_x*sargs.segments)
-    return;
-  const int segment=item/args.tiles_x,strip=item-segment*args.tiles_x;
-  const int step_begin=segment*sargs.steps_per_segment;
-  const int step_end=step_begin+sargs.steps_per_segment < args.tiles_y ? step_begin+sargs.steps_per_segment : args.tiles_y;
-  const int valid_w=64*SX-2*hmax;
-  const int bx=strip*valid_w;
-
-  // ---- source access: tile column t is image column bx+cx-hmax+t, clamped (cache.c:2663-2679);
-  // a lane keeps its four columns for the whole walk.  Lanes whose four columns are inside the
-  // frame (all but a few of the first and the last strip) fetch straight into LDS; the others
-  // through registers.
-  const int sx=bx+args.cx-hmax+SX*lane;
-  const bool inside=(sx >= 0) && (sx+SX-1 <= W-1);
-  unsigned xoff[SX];
-#pragma unroll
-  for (int j=0; j < SX; j++)
-    {
-      int x=sx+j;
-      x=x < 0 ? 0 : (x > W-1 ? W-1 : x);
-      xoff[j]=(unsigned) x*(unsigned) (C*sizeof(uint16_t));
-    }
-  const unsigned row_bytes=(unsigned) W*(unsigned) (C*sizeof(uint16_t));
-  const unsigned char *base=reinterpret_cast<const unsigned char *>(args.src);
-  const unsigned lds_base=(unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) smem_raw;
-  auto ring_at=[&](int row,int half) -> Half * { return ring+(size_t) (row*2+half)*64+lane; };
-  // image row sy -> ring row `row`; `held`: the columns of a lane at the frame's edge
-  auto fetch_row=[&](int sy,int row,Half (&held)[2])
-  {
-    sy=sy < 0 ? 0 : (sy > H-1 ? H-1 : sy);
-    const unsigned at=(unsigned) sy*row_bytes;
-    if (inside)
-      {
-        if constexpr (C == 4)
-          {
-            // 64 lanes x 16 bytes land at M0 + 16*lane: one (row, half) plane of the ring
-            const unsigned to=(unsigned) __builtin_amdgcn_readfirstlane((int) (lds_base+(unsigned) row*2048u));
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %2"
-                         : : "s"(to),"v"(at+xoff[0]),"s"(base),"s"(to+1024u),"v"(at+xoff[2]) : "memory");
-          }
-        else
-          {
-            held[0]=*reinterpret_cast<const LooseHalf *>(base+at+xoff[0]);
-            held[1]=*reinterpret_cast<const LooseHalf *>(base+at+xoff[2]);
-          }
-      }
-    else
-      {
-#pragma unroll
-        for (int j=0; j < SX; j++)
-#pragma unroll
-          for (int w=0; w < NW; w++)
-            held[j >> 1][(j & 1)*NW+w]=*reinterpret_cast<const uint32_t *>(base+at+xoff[j]+4*w);
-      }
-  };
-  auto commit_row=[&](int row,const Half (&held)[2])
-  {
-    if ((C != 4) || !inside)
-      {
-        *ring_at(row,0)=held[0];
-        *ring_at(row,1)=held[1];
-      }
-  };
-  auto wrapped=[&](int row) { return row >= R ? row-R : row; };
-
-  // tile row q of step s is image row s*TH+cy-vmax+q and ring row (origin+q) mod R, `origin`
-  // advancing by TH a step
-  int origin=0;
-  {
-    const int sy0=step_begin*TH+args.cy-vmax;
-    for (int q=wave; q < halo+TH; q+=NWAVES)
-      {
-        Half held[2];
-        fetch_row(sy0+q,q,held);
-        commit_row(q,held);
-      }
-  }
-  Half held[SY][2];                            // the new rows of the next step, frame-edge lanes
-  // lane l keeps level l's reach and widening (a v_readlane per level instead of a load from the
-  // kernel arguments, whose latency nothing hides)
-  const int lane_reach=lane < args.nlevels ? (int) args.reach[lane] : 0;
-  const int lane_widen=lane < args.nlevels ? (int) args.widen[lane] : 0;
-  const int u0=SX*lane-hmax;                   // first of the lane's columns within the valid span
-  const bool centred=(args.cx == 0) && (args.cy == 0);
-  bool ok[SX];
-  bool all=true;
-#pragma unroll
-  for (int j=0; j < SX; j++)
-    {
-      ok[j]=(u0+j >= 0) && (u0+j < valid_w) && (bx+u0+j < W);
-      all=all && ok[j];
-    }
-  unsigned changed=0;
-  // the results of a step are stored at the beginning of the next one: the s_waitcnt vmcnt(0) that
-  // ends a step (the fetched rows are in LDS) would otherwise wait for the stores just issued
-  uint32_t result[SY][WPR];
-  int result_by=-1;
-  auto store_results=[&]()
-  {
-    if (result_by < 0)
-      return;
-#pragma unroll
-    for (int i=0; i < SY; i++)
-      {
-        const int y=result_by+wave*SY+i;
-        if (y >= H)
-          break;
-        unsigned char *out=reinterpret_cast<unsigned char *>(args.dst)+(unsigned) y*row_bytes;
-        if (all)
-          {
-            Half lo,hi;
-#pragma unroll
-            for (int p=0; p < HW; p++)
-              {
-                lo[p]=result[i][p];
-                hi[p]=result[i][HW+p];
-              }
-            unsigned char *at=out+(unsigned) (bx+u0)*(unsigned) (C*sizeof(uint16_t));
-            *reinterpret_cast<LooseHalf *>(at)=lo;
-            *reinterpret_cast<LooseHalf *>(at+sizeof(Half))=hi;
-          }
-        else
-          {
-#pragma unroll
-            for (int j=0; j < SX; j++)
-              if (ok[j])
-#pragma unroll
-                for (int w=0; w < NW; w++)
-                  *reinterpret_cast<uint32_t *>(out+(unsigned) (bx+u0+j)*(unsigned) (C*sizeof(uint16_t))+4*w)=result[i][j*NW+w];
-          }
-      }
-  };
-  for (int step=step_begin; step < step_end; step++)
-    {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the rows fetched for this step are in LDS
-      __syncthreads();                                     // ... everybody's, and the previous tile is done with
-      if (step+1 < step_end)
-        {
-          // the TH new rows of step+1: tile rows halo+TH .. halo+2*TH-1 of this step
-          const int sy0=(step+1)*TH+args.cy-vmax+halo;
-#pragma unroll
-          for (int j=0; j < SY; j++)
-            fetch_row(sy0+wave+NWAVES*j,wrapped(wrapped(origin+TH)+halo+wave+NWAVES*j),held[j]);
-        }
-
-      // ---- the wave's two output rows: tile rows centre, centre+1
-      const int by=step*TH;
-      const int centre=origin+vmax+wave*SY;      // < 2R: wrapped() per access
-      uint32_t column[SY][WPR],spread[SY][WPR];    // C and S of the header above morph_rects_kernel
-      // rows centre-k (`up`) and centre+1+k (`down`) of three successive depths k: the previous
-      // one, the one being folded in and the next one, whose reads are already under way;
-      // depth 0: the output rows themselves
-      Half up[3][2],down[3][2];
-      auto read_depth=[&](int k,Half (&to_up)[2],Half (&to_down)[2])
-      {
-        const int above=wrapped(centre-k),below=wrapped(wrapped(centre+1+k));     // centre-k >= origin >= 0
-        to_up[0]=*ring_at(above,0);
-        to_up[1]=*ring_at(above,1);
-        to_down[0]=*ring_at(below,0);
-        to_down[1]=*ring_at(below,1);
-      };
-      read_depth(0,up[0],down[0]);
-      if (vmax >= 1)
-        read_depth(1,up[1],down[1]);
-#pragma unroll
-      for (int p=0; p < WPR; p++)
-        {
-          column[0][p]=up[0][p/HW][p%HW];
-          column[1][p]=down[0][p/HW][p%HW];
-          spread[0][p]=DILATE ? 0u : 0xffffffffu;
-          spread[1][p]=DILATE ? 0u : 0xffffffffu;
-        }
-      // depth k: row 0 takes centre-k (new `up`) and centre+k (previous `down`), row 1 takes
-      // centre+1-k (previous `up`) and centre+1+k (new `down`)
-      auto fold=[&](const Half (&new_up)[2],const Half (&new_down)[2],const Half (&old_up)[2],const Half (&old_down)[2])
-      {
-#pragma unroll
-        for (int p=0; p < WPR; p++)
-          {
-            column[0][p]=pk_pick<DILATE>(pk_pick<DILATE>(column[0][p],new_up[p/HW][p%HW]),old_down[p/HW][p%HW]);
-            column[1][p]=pk_pick<DILATE>(pk_pick<DILATE>(column[1][p],old_up[p/HW][p%HW]),new_down[p/HW][p%HW]);
-          }
-      };
-      // every level whose reach the fold depth has arrived at: merge the column windows into the
-      // spread and widen it (the levels' reaches grow as l falls)
-      int level=args.nlevels-1;
-      auto settle=[&](int depth)
-      {
-        while ((level >= 0) && (__builtin_amdgcn_readlane(lane_reach,level) <= depth))
-          {
-#pragma unroll
-            for (int i=0; i < SY; i++)
-#pragma unroll
-              for (int p=0; p < WPR; p++)
-                spread[i][p]=pk_pick<DILATE>(spread[i][p],column[i][p]);
-            const int widen=__builtin_amdgcn_readlane(lane_widen,level);
-            for (int stride=0; stride < widen; stride++)
-              {
-                // Row(1) over the lane's columns a b c d and the neighbours' d' (left) and a' (right):
-                //   a <- d' v (a v b),  b <- (a v b) v c,  c <- b v (c v d),  d <- (c v d) v a'
-#pragma unroll
-                for (int i=0; i < SY; i++)
-#pragma unroll
-                  for (int w=0; w < NW; w++)
-                    {
-                      const uint32_t a=spread[i][w],b=spread[i][NW+w],c=spread[i][2*NW+w],d=spread[i][3*NW+w];
-                      // wave_shr:1 — lane n reads lane n-1 (0x138); wave_shl:1 — lane n reads lane n+1 (0x130)
-                      const uint32_t left=(uint32_t) __builtin_amdgcn_mov_dpp((int) d,0x138,0xf,0xf,true);
-                      const uint32_t right=(uint32_t) __builtin_amdgcn_mov_dpp((int) a,0x130,0xf,0xf,true);
-                      const uint32_t ab=pk_pick<DILATE>(a,b),cd=pk_pick<DILATE>(c,d);
-                      spread[i][w]=pk_pick<DILATE>(left,ab);
-                      spread[i][NW+w]=pk_pick<DILATE>(ab,c);
-                      spread[i][2*NW+w]=pk_pick<DILATE>(b,cd);
-                      spread[i][3*NW+w]=pk_pick<DILATE>(cd,right);
-                    }
-              }
-            level--;
-          }
-      };
-      // the fold depths in threes, so that which register set holds which depth's rows is known at
-      // compile time
-      settle(0);
-      for (int k=1; k <= vmax; k+=3)
-        {
-          // the previous step's rows leave here, apart from the burst of fetches at the step's start
-          // (measured: 2.25 -> 2.10 ms against storing them first thing)
-          if (k == kStoreDepth)
-            store_results();
-          if (k+1 <= vmax)
-            read_depth(k+1,up[2],down[2]);
-          fold(up[1],down[1],up[0],down[0]);
-          settle(k);
-          if (k+1 <= vmax)
-            {
-              if (k+2 <= vmax)
-                read_depth(k+2,up[0],down[0]);
-              fold(up[2],down[2],up[1],down[1]);
-              settle(k+1);
-            }
-          if (k+2 <= vmax)
-            {
-              if (k+3 <= vmax)
-                read_depth(k+3,up[1],down[1]);
-              fold(up[0],down[0],up[2],down[2]);
-              settle(k+2);
-            }
-        }
-
-      if (vmax < kStoreDepth)
-        store_results();
-      // ---- copy out: morphology.c:3180-3196 (channels without the update trait keep the source
-      // value; `changed` counts the updated samples that differ from the source)
-#pragma unroll
-      for (int i=0; i < SY; i++)
-        {
-          const int y=by+wave*SY+i;
-          if (y >= H)
-            break;
-          if (DILATE && (args.copy_mask == 0u) && (args.changed == nullptr))
-            {
-              // every channel updated, nobody counts: the maxima are the result
-#pragma unroll
-              for (int p=0; p < WPR; p++)
-                result[i][p]=spread[i][p];
-            }
-          else
-            {
-              uint32_t original[WPR];
-              if (centred)
-                {
-                  // the output pixel is the centre of its own window
-                  const Half a=*ring_at(wrapped(centre+i),0),b=*ring_at(wrapped(centre+i),1);
-#pragma unroll
-                  for (int p=0; p < HW; p++)
-                    {
-                      original[p]=a[p];
-                      original[HW+p]=b[p];
-                    }
-                }
-              else
-                {
-                  const unsigned char *in=base+(unsigned) y*row_bytes;
-#pragma unroll
-                  for (int j=0; j < SX; j++)
-#pragma unroll
-                    for (int w=0; w < NW; w++)
-                      original[j*NW+w]=ok[j] ? *reinterpret_cast<const uint32_t *>(in+(unsigned) (bx+u0+j)*(unsigned) (C*sizeof(uint16_t))+4*w) : 0u;
-                }
-#pragma unroll
-              for (int p=0; p < WPR; p++)
-                {
-                  // Erode starts from the output pixel itself (morphology.c:2905-2912)
-                  const uint32_t value=DILATE ? spread[i][p] : pk_pick<false>(spread[i][p],original[p]);
-                  const int c0=2*(p % NW);             // channels of this word's halves
-                  uint32_t keep=0u;
-                  keep|=((args.copy_mask >> c0) & 1u) != 0u ? 0x0000ffffu : 0u;
-                  keep|=((args.copy_mask >> (c0+1)) & 1u) != 0u ? 0xffff0000u : 0u;
-                  result[i][p]=(original[p] & keep) | (value & ~keep);
-                  const uint32_t differs=(value ^ original[p]) & ~keep;
-                  if (ok[p/NW])
-                    changed+=((differs & 0xffffu) != 0u ? 1u : 0u)+((differs >> 16) != 0u ? 1u : 0u);
-                }
-            }
-        }
-      result_by=by;
-      if (step+1 < step_end)
-        {
-          // rows that came through registers (nobody reads these ring rows during this step)
-#pragma unroll
-          for (int j=0; j < SY; j++)
-            commit_row(wrapped(wrapped(origin+TH)+halo+wave+NWAVES*j),held[j]);
-        }
-      origin=wrapped(origin+TH);
-    }
-  store_results();
-  if (args.changed != nullptr)
-    {
-      changed=wave_sum(changed);
-      if ((lane == 0) && (changed != 0))
-        atomicAdd(args.changed,(unsigned long long) changed);
-    }
-}
-
-template<int C,bool DILATE>
-static MhStatus launch_strips_typed(const StripsArgs &args,size_t lds,hipStream_t stream)
-{
-  constexpr int WAVES=12;
-  const dim3 grid(8u*(unsigned) args.items_per_xcd),block(64*WAVES);
-  MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&morph_strips_kernel<C,DILATE,WAVES>),
-    hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
-  hipLaunchKernelGGL((morph_strips_kernel<C,DILATE,WAVES>),grid,block,lds,stream,args);
-  MH_HIP(hipGetLastError());
-  return MH_OK;
 }
 
 static MhStatus try_rects(const View &src,const View &dst,bool dilate,const std::vector<int> &half,
@@ -1520,13 +1129,7 @@ static MhStatus try_rects(const View &src,const View &dst,bool dilate,const std:
   const int lane_columns=pixel_bytes >= 16 ? 1 : 2;
   const int wave_columns=64*lane_columns;
   const size_t row_lds=(size_t) wave_columns*pixel_bytes;
-  int shape=1;
-  if (const char *e=option("MAGICKHIP_RECTS_SHAPE"))
-    shape=(atoi(e) >= 0) && (atoi(e) <= 3) ? atoi(e) : 0;
-  if (is_float)
-    shape=1;
-  const int th=shape == 2 ? 96 : 48;
-  const size_t lds=(size_t) (th+2*vmax)*row_lds;
+  const size_t lds=(size_t) (kRectsRows+2*vmax)*row_lds;
   if ((wave_columns-2*hmax < 16) || (lds > 160u*1024u))
     return MH_OK;
   RectsArgs a;
@@ -1556,72 +1159,24 @@ static MhStatus try_rects(const View &src,const View &dst,bool dilate,const std:
   a.vmax=vmax;
   a.copy_mask=roles.copy_mask;
   a.changed=changed;
-  {
-    // frames of several strips by several steps: the walk down 256-column strips.  Opt-in
-    // (MAGICKHIP_STRIPS=1): on MI355X it reads the frame 1.13 times instead of 1.31 but takes
-    // 2.10 ms where the tile kernel takes 1.95 (16384^2 RGBA, Disk:15) — three waves a SIMD hide
-    // less than the tile kernel's six (profiles/r3_notes/dilate_experiments.txt).
-    constexpr int kStripRows=24;
-    const size_t strip_lds=(size_t) (2*kStripRows+2*vmax)*2u*row_lds;
-    const int strip_w=256-2*hmax;
-    if (!is_float && ((unsigned long long) src.columns*src.rows*pixel_bytes < (1ull << 32)) &&
-        (strip_lds <= 160u*1024u) && ((int) src.columns >= 2*strip_w) &&
-        ((int) src.rows >= 4*kStripRows) && (option("MAGICKHIP_STRIPS") != nullptr))
-      {
-        StripsArgs sa;
-        sa.r=a;
-        sa.r.tiles_x=((int) src.columns+strip_w-1)/strip_w;
-        sa.r.tiles_y=((int) src.rows+kStripRows-1)/kStripRows;
-        // cuts of a strip: the schedule (one workgroup per CU, 256 CUs) that finishes first; a
-        // cut costs its 2*vmax rows of halo
-        int best=1;
-        double best_cost=1.0e300;
-        for (int cuts=1; cuts <= sa.r.tiles_y; cuts++)
-          {
-            const int steps=(sa.r.tiles_y+cuts-1)/cuts;
-            const int rounds=(sa.r.tiles_x*((sa.r.tiles_y+steps-1)/steps)+255)/256;
-            const double cost=(double) rounds*((double) (steps+1)*kStripRows+2.0*vmax);
-            if (cost < best_cost-1.0e-9)
-              {
-                best_cost=cost;
-                best=cuts;
-              }
-          }
-        if (const char *e=option("MAGICKHIP_STRIP_CUTS"))         // tests: walks of several steps on small frames
-          best=(atoi(e) >= 1) && (atoi(e) <= sa.r.tiles_y) ? atoi(e) : best;
-        sa.steps_per_segment=(sa.r.tiles_y+best-1)/best;
-        sa.segments=(sa.r.tiles_y+sa.steps_per_segment-1)/sa.steps_per_segment;
-        sa.items_per_xcd=(sa.r.tiles_x*sa.segments+7)/8;
-        sa.r.tiles_per_xcd=sa.items_per_xcd;
-        ProfileScope prof("morph_rects",src.stream);
-        if (src.channels == 4)
-          MH_TRY((dilate ? launch_strips_typed<4,true>(sa,strip_lds,src.stream) : launch_strips_typed<4,false>(sa,strip_lds,src.stream)));
-        else
-          MH_TRY((dilate ? launch_strips_typed<2,true>(sa,strip_lds,src.stream) : launch_strips_typed<2,false>(sa,strip_lds,src.stream)));
-        *handled=true;
-        return MH_OK;
-      }
-  }
   const int valid_w=wave_columns-2*hmax;
   a.tiles_x=((int) src.columns+valid_w-1)/valid_w;
-  a.tiles_y=((int) src.rows+th-1)/th;
+  a.tiles_y=((int) src.rows+kRectsRows-1)/kRectsRows;
   a.tiles_per_xcd=(a.tiles_x*a.tiles_y+7)/8;
-  a.copy_mask=roles.copy_mask;
-  a.changed=changed;
   ProfileScope prof("morph_rects",src.stream);
   if (is_float)
     {
       if (src.channels == 4)
-        MH_TRY((launch_rects<float,4>(dilate,shape,a,lds,src.stream)));
+        MH_TRY((launch_rects<float,4>(dilate,a,lds,src.stream)));
       else if (src.channels == 2)
-        MH_TRY((launch_rects<float,2>(dilate,shape,a,lds,src.stream)));
+        MH_TRY((launch_rects<float,2>(dilate,a,lds,src.stream)));
       else
-        MH_TRY((launch_rects<float,1>(dilate,shape,a,lds,src.stream)));
+        MH_TRY((launch_rects<float,1>(dilate,a,lds,src.stream)));
     }
   else if (src.channels == 4)
-    MH_TRY((launch_rects<uint16_t,4>(dilate,shape,a,lds,src.stream)));
+    MH_TRY((launch_rects<uint16_t,4>(dilate,a,lds,src.stream)));
   else
-    MH_TRY((launch_rects<uint16_t,2>(dilate,shape,a,lds,src.stream)));
+    MH_TRY((launch_rects<uint16_t,2>(dilate,a,lds,src.stream)));
   *handled=true;
   return MH_OK;
 }
@@ -1807,7 +1362,7 @@ MhStatus launch_morph2d(const View &src,const View &dst,const Morph2DParams &par
         c.value=value;
         cells.push_back(c);
       }
-  if (((mc == MC_ERODE) || (mc == MC_DILATE)) && (option("MAGICKHIP_NO_CONVEX") == nullptr))
+  if ((mc == MC_ERODE) || (mc == MC_DILATE))
     {
       bool handled=false;
       MH_TRY(try_convex(src,dst,mc == MC_DILATE,cells,roles,changed,&handled));

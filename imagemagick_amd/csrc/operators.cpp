@@ -383,7 +383,7 @@ static MhStatus primitive(const View &src,const View &dst,MhMorphologyMethod met
       (src.quantum == MH_QUANTUM_F32) && ((src.channels == 4) || ((src.channels == 3) && !roles.blend)) &&
       (roles.copy_mask == 0) && (!roles.blend || (roles.alpha == 3)) &&
       (option("MAGICKHIP_NO_MFMA") == nullptr) && (option("MAGICKHIP_NO_MFMA_2D") == nullptr) &&
-      (option("MAGICKHIP_NO_EXACT_2D") == nullptr) && (option("MAGICKHIP_NO_EXACT_2D_FLOAT") == nullptr))
+      (option("MAGICKHIP_NO_EXACT_2D") == nullptr))
     {
       // (outer products — boxes — have the separable path below, which takes any float frame)
       std::vector<double> row,column;
@@ -680,11 +680,11 @@ static MhStatus fused_blur(const View &src,const View &dst,const MhKernelInfo *k
     }
   // EXACT BlurImage of an alpha-weighted frame: the kernel may give the frame up (alpha of a few
   // levels everywhere: BlurExactArgs::give_up); the two fp64 passes queued behind it — bit-identical
-  // too — then compute it, and leave at once otherwise.  MAGICKHIP_NO_GIVE_UP=1: never.  Without the
+  // too — then compute it, and leave at once otherwise.  Without the
   // memory for those passes' intermediate the kernel runs unguarded (it is exact either way, only slow
   // on such frames).
   Temp give_up,rows_memory;
-  bool guarded=exact && !unsharp && roles.blend && (option("MAGICKHIP_NO_GIVE_UP") == nullptr);
+  bool guarded=exact && !unsharp && roles.blend;
   if (guarded)
     {
       if ((give_up.alloc(src.device,sizeof(unsigned),src.stream) != MH_OK) ||

@@ -546,7 +546,7 @@ static MhStatus colorspace_step(const View &img,int op)
       MH_HIP(hipGetLastError());
       return MH_OK;
     }
-  if ((img.quantum == MH_QUANTUM_U16) && (option("MAGICKHIP_NO_COLOR_TABLES") == nullptr) &&
+  if ((img.quantum == MH_QUANTUM_U16) &&
       ((op == OP_SRGB_TO_RGB) || (op == OP_RGB_TO_SRGB) || (op == OP_SRGB_TO_LAB) ||
        (op == OP_SRGB_TO_XYZ)))
     {
@@ -1329,8 +1329,7 @@ MhStatus launch_lab_fast_with_histogram(const View &img,const MhImage *lab_desc,
   if ((img.quantum != MH_QUANTUM_U16) || (img.channels != 4) || (precision() != MH_PRECISION_FAST) ||
       (n < ((size_t) 1 << 20)) || (n >= ((size_t) 1 << 31)) ||
       ((reinterpret_cast<uintptr_t>(img.pixels) & 15u) != 0) ||
-      (option("MAGICKHIP_NO_FAST_LAB") != nullptr) || (option("MAGICKHIP_NO_PACKED_HISTOGRAM") != nullptr) ||
-      (option("MAGICKHIP_NO_LDS_HISTOGRAM") != nullptr) || (option("MAGICKHIP_NO_FUSED_LAB_HISTOGRAM") != nullptr))
+      (option("MAGICKHIP_NO_FAST_LAB") != nullptr) || (option("MAGICKHIP_NO_PACKED_HISTOGRAM") != nullptr))
     return MH_OK;
   const size_t nblocks=packed_histogram_blocks(img.device,n);
   if (nblocks == 0)
@@ -1373,7 +1372,6 @@ MhStatus launch_lab_fast_contrast_stretch(const View &img,const MhImage *lab_des
       (n < ((size_t) 1 << 20)) || (n >= ((size_t) 1 << 31)) ||
       ((reinterpret_cast<uintptr_t>(img.pixels) & 15u) != 0) ||
       (option("MAGICKHIP_NO_FAST_LAB") != nullptr) || (option("MAGICKHIP_NO_PACKED_HISTOGRAM") != nullptr) ||
-      (option("MAGICKHIP_NO_LDS_HISTOGRAM") != nullptr) || (option("MAGICKHIP_NO_FUSED_LAB_HISTOGRAM") != nullptr) ||
       (option("MAGICKHIP_NO_STRETCH_LEVELS") != nullptr))
     return MH_OK;
   const size_t nblocks=packed_histogram_blocks(img.device,n);
@@ -1436,7 +1434,7 @@ static MhStatus histogram_typed(const View &src,int mode,const IntensityParams &
   const size_t n=src.columns*src.rows;
   // large frames in intensity mode: the LDS-privatised kernel (a frame below ~1 Mpixel
   // does not amortise the 2 x 256 x 128 KB slab traffic)
-  if ((mode != 0) && (n >= ((size_t) 1 << 20)) && (option("MAGICKHIP_NO_LDS_HISTOGRAM") == nullptr))
+  if ((mode != 0) && (n >= ((size_t) 1 << 20)))
     {
       // one pass with 16-bit counters, Q16 and float Quantum alike (the bin of a float sample is
       // ScaleQuantumToMap's)

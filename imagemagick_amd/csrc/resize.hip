@@ -435,8 +435,8 @@ MhStatus launch_resize_fused(const View &src,const View &dst,const TapTable &ver
         return MH_OK;
     }
   // any other enlargement of a four-channel frame: both filters on the fp64 matrix pipe, the
-  // intermediate in registers (resize_mfma.hip); MAGICKHIP_NO_RESIZE_MFMA=1 keeps the two passes
-  if ((option("MAGICKHIP_NO_RESIZE_MFMA") == nullptr) && (pixels >= matrix_from))
+  // intermediate in registers (resize_mfma.hip)
+  if (pixels >= matrix_from)
     return launch_resize_mfma(src,dst,vertical,horizontal,roles,handled);
   return MH_OK;
 }
@@ -725,16 +725,12 @@ static MhStatus launch_typed(const View &src,const View &dst,bool vertical,
           if ((size_t) lds_span*cpx <= 150u*1024u)
             {
               int tile_rows=(int) (budget/((size_t) lds_span*cpx));
-              int cap=16;
-              if (const char *e=option("MAGICKHIP_HTILE"))
-                cap=atoi(e);
-              tile_rows=tile_rows < 1 ? 1 : (tile_rows > cap ? cap : tile_rows);
+              tile_rows=tile_rows < 1 ? 1 : (tile_rows > 16 ? 16 : tile_rows);
               size_t lds=(size_t) lds_span*cpx*(size_t) tile_rows;
               dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) ((dst.rows+tile_rows-1)/tile_rows));
               ProfileScope prof("resize_horizontal",src.stream);
               constexpr bool kCanPremultiply=ResizeAcc<Q,C,BLEND,A>::kDerive;
-              const bool premultiply=kCanPremultiply && (args.copy_mask == 0) &&
-                (option("MAGICKHIP_NO_RESIZE_PREMULTIPLY") == nullptr);
+              const bool premultiply=kCanPremultiply && (args.copy_mask == 0);
 #define MH_LAUNCH_H(N)                                                                        \
               {                                                                                \
                 if (premultiply)                                                               \

@@ -408,7 +408,7 @@ struct MfmaPlanDevice
 
 struct MfmaPlanEntry
 {
-  unsigned long long vserial,hserial; int device,tps,waves; std::shared_ptr<MfmaPlanDevice> plan;
+  unsigned long long vserial,hserial; int device,tps; std::shared_ptr<MfmaPlanDevice> plan;
 };
 static std::mutex &mfma_plans_lock() { static std::mutex &m=*new std::mutex; return m; }
 static std::vector<MfmaPlanEntry> &mfma_plans() { static std::vector<MfmaPlanEntry> &v=*new std::vector<MfmaPlanEntry>; return v; }
@@ -419,10 +419,14 @@ void release_resize_mfma_plans()
   mfma_plans().clear();
 }
 
-static MhStatus build_plan_device(MfmaPlanDevice &d,const TapTable &vt,const TapTable &ht,int tps,int waves,
-  int device,hipStream_t stream)
+// Four waves a workgroup: three workgroups = three waves a SIMD fit a CU's LDS (weights 24 KB + patch 29 KB each for
+// a 4x Lanczos); six waves a workgroup measured 5.75 ms against 4.83 (8192^2 -> 32768^2, profiles/r5_notes).
+constexpr int kMfmaWaves=4;
+
+static MhStatus build_plan_device(MfmaPlanDevice &d,const TapTable &vt,const TapTable &ht,int tps,int device,
+  hipStream_t stream)
 {
-  d.ok=build_mfma_resize_plan(d.plan,vt,ht,tps,waves);
+  d.ok=build_mfma_resize_plan(d.plan,vt,ht,tps,kMfmaWaves);
   if (!d.ok)
     return MH_OK;
   const MfmaResizePlan &p=d.plan;
@@ -444,7 +448,7 @@ static MhStatus build_plan_device(MfmaPlanDevice &d,const TapTable &vt,const Tap
 }
 
 static MhStatus acquire_plan(std::shared_ptr<MfmaPlanDevice> *out,const TapTable &vt,const TapTable &ht,int tps,
-  int waves,int device,hipStream_t stream)
+  int device,hipStream_t stream)
 {
   const bool shared=(vt.serial != 0) && (ht.serial != 0);
   constexpr size_t kEntries=16;
@@ -454,7 +458,7 @@ static MhStatus acquire_plan(std::shared_ptr<MfmaPlanDevice> *out,const TapTable
       std::vector<MfmaPlanEntry> &entries=mfma_plans();
       for (size_t i=0; i < entries.size(); i++)
         if ((entries[i].vserial == vt.serial) && (entries[i].hserial == ht.serial) &&
-            (entries[i].device == device) && (entries[i].tps == tps) && (entries[i].waves == waves))
+            (entries[i].device == device) && (entries[i].tps == tps))
           {
             MfmaPlanEntry hit=entries[i];
             entries.erase(entries.begin()+(ptrdiff_t) i);
@@ -466,7 +470,7 @@ static MhStatus acquire_plan(std::shared_ptr<MfmaPlanDevice> *out,const TapTable
           }
     }
   auto built=std::make_shared<MfmaPlanDevice>();
-  MH_TRY(build_plan_device(*built,vt,ht,tps,waves,device,stream));
+  MH_TRY(build_plan_device(*built,vt,ht,tps,device,stream));
   *out=built;
   // (the evicted plan is released after the lock: its destructor drains the device)
   std::shared_ptr<MfmaPlanDevice> evicted;
@@ -474,7 +478,7 @@ static MhStatus acquire_plan(std::shared_ptr<MfmaPlanDevice> *out,const TapTable
     {
       std::lock_guard<std::mutex> guard(mfma_plans_lock());
       std::vector<MfmaPlanEntry> &entries=mfma_plans();
-      entries.insert(entries.begin(),MfmaPlanEntry{vt.serial,ht.serial,device,tps,waves,built});
+      entries.insert(entries.begin(),MfmaPlanEntry{vt.serial,ht.serial,device,tps,built});
       if (entries.size() > kEntries)
         {
           evicted=std::move(entries.back().plan);
@@ -530,26 +534,25 @@ static MhStatus launch_mfma_typed(const View &src,const View &dst,const MfmaPlan
   return MH_OK;
 }
 
-template<int WAVES,int NK>
-static MhStatus launch_mfma_waves(const View &src,const View &dst,const MfmaPlanDevice &d,int steps,bool blend)
+template<int NK>
+static MhStatus launch_mfma_quantum(const View &src,const View &dst,const MfmaPlanDevice &d,int steps,bool blend)
 {
   if (src.quantum == MH_QUANTUM_U16)
-    return blend ? launch_mfma_typed<uint16_t,true,WAVES,NK>(src,dst,d,steps) :
-                   launch_mfma_typed<uint16_t,false,WAVES,NK>(src,dst,d,steps);
-  return blend ? launch_mfma_typed<float,true,WAVES,NK>(src,dst,d,steps) :
-                 launch_mfma_typed<float,false,WAVES,NK>(src,dst,d,steps);
+    return blend ? launch_mfma_typed<uint16_t,true,kMfmaWaves,NK>(src,dst,d,steps) :
+                   launch_mfma_typed<uint16_t,false,kMfmaWaves,NK>(src,dst,d,steps);
+  return blend ? launch_mfma_typed<float,true,kMfmaWaves,NK>(src,dst,d,steps) :
+                 launch_mfma_typed<float,false,kMfmaWaves,NK>(src,dst,d,steps);
 }
 
-template<int WAVES>
 static MhStatus launch_mfma_blocks(const View &src,const View &dst,const MfmaPlanDevice &d,int steps,bool blend)
 {
   switch (d.plan.nk)
   {
-    case 1: return launch_mfma_waves<WAVES,1>(src,dst,d,steps,blend);
-    case 2: return launch_mfma_waves<WAVES,2>(src,dst,d,steps,blend);
-    case 3: return launch_mfma_waves<WAVES,3>(src,dst,d,steps,blend);
-    case 4: return launch_mfma_waves<WAVES,4>(src,dst,d,steps,blend);
-    default: return launch_mfma_waves<WAVES,5>(src,dst,d,steps,blend);
+    case 1: return launch_mfma_quantum<1>(src,dst,d,steps,blend);
+    case 2: return launch_mfma_quantum<2>(src,dst,d,steps,blend);
+    case 3: return launch_mfma_quantum<3>(src,dst,d,steps,blend);
+    case 4: return launch_mfma_quantum<4>(src,dst,d,steps,blend);
+    default: return launch_mfma_quantum<5>(src,dst,d,steps,blend);
   }
 }
 
@@ -567,18 +570,9 @@ MhStatus launch_resize_mfma(const View &src,const View &dst,const TapTable &vert
   // enlargements only: a reduction's windows are wider than the two blocks the ring holds
   if ((dst.rows < src.rows) || (dst.columns < src.columns))
     return MH_OK;
-  // 16 tiles (256 columns) a strip, four waves a workgroup: three workgroups = three waves a SIMD
-  // fit a CU's LDS (weights 24 KB + patch 29 KB each for a 4x Lanczos); measured 4.83 ms against
-  // 5.75 with six waves a workgroup (8192^2 -> 32768^2, profiles/r5_notes)
-  int tps=16,steps=8,waves=4;
-  if (const char *e=option("MAGICKHIP_RESIZE_MFMA_TPS"))
-    tps=atoi(e) > 0 ? atoi(e) : tps;
-  if (const char *e=option("MAGICKHIP_RESIZE_MFMA_STEPS"))
-    steps=atoi(e) > 0 ? atoi(e) : steps;
-  if (const char *e=option("MAGICKHIP_RESIZE_MFMA_WAVES"))
-    waves=atoi(e);
-  if ((waves != 4) && (waves != 6))
-    waves=4;
+  // 16 tiles (256 columns) a strip, 8 steps down the image a workgroup
+  int tps=16;
+  constexpr int steps=8;
   // (sized for the 160 KiB of a gfx950 CU: two workgroups of up to 78 KiB; a part with less declines)
   if (lds_bytes_per_workgroup(src.device) < 160*1024)
     return MH_OK;
@@ -587,18 +581,16 @@ MhStatus launch_resize_mfma(const View &src,const View &dst,const TapTable &vert
   // barely-enlarging geometry's wide patch gets narrower strips)
   for ( ; ; tps/=2)
     {
-      MH_TRY(acquire_plan(&plan,vertical,horizontal,tps,waves,src.device,src.stream));
+      MH_TRY(acquire_plan(&plan,vertical,horizontal,tps,src.device,src.stream));
       if (!plan->ok || (plan->plan.nk > 5))
         return MH_OK;
-      if ((mfma_lds_bytes(plan->plan) <= 78u*1024u) && (16*plan->plan.nvb_max <= 64*waves))
+      if ((mfma_lds_bytes(plan->plan) <= 78u*1024u) && (16*plan->plan.nvb_max <= 64*kMfmaWaves))
         break;
       if (tps <= 4)
         return MH_OK;
     }
   *handled=true;
-  if (waves == 4)
-    return launch_mfma_blocks<4>(src,dst,*plan,steps,roles.blend);
-  return launch_mfma_blocks<6>(src,dst,*plan,steps,roles.blend);
+  return launch_mfma_blocks(src,dst,*plan,steps,roles.blend);
 }
 
 } // namespace mh

@@ -221,7 +221,7 @@ MH_API MhPrecision MhSetPrecision(MhPrecision precision);
    initialises (MhInitialize or the first call); later changes of the environment are not seen.
    MhSetOption changes the value the library holds (value == NULL: as if the variable were unset)
    — for tests and A/B measurements; MhGetOption returns it (NULL when unset; the pointer stays
-   valid).  Names as documented in DESIGN.md, e.g. "MAGICKHIP_NO_EXACT_MFMA". */
+   valid).  Names as documented in DESIGN.md, e.g. "MAGICKHIP_NO_MFMA". */
 MH_API MhStatus MhSetOption(const char *name,const char *value);
 MH_API const char *MhGetOption(const char *name);
 

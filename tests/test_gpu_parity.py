@@ -1125,41 +1125,28 @@ def test_float_rects_channel_mask_change_count_and_nan(im, refmod):
         assert same.all(), "%s with NaN samples: %d differ" % (method, int((~same).sum()))
 
 
-@pytest.mark.parametrize("channels,cuts", [(4, 1), (4, 2), (2, 1), (4, None)])
+@pytest.mark.parametrize("channels", [4, 2])
 @pytest.mark.parametrize("method,kernel", [
     ("Dilate", "Disk:15"), ("Erode", "Disk:15"), ("Erode", "Octagon:6"), ("Dilate", "Square:3"),
     ("Dilate", "Rectangle:9x5+2+1"), ("Erode", "Diamond:11"), ("Dilate", "Rectangle:1x9"), ("Erode", "Rectangle:13x1"),
 ])
-def test_symmetric_convex_kernels_down_a_strip(im, refmod, method, kernel, channels, cuts, options):
-    """The same union-of-rectangles evaluation as a walk down 256-column strips (morph_strips_kernel,
-    opt-in with MAGICKHIP_STRIPS=1: four columns per lane, a ring of rows in LDS that
-    global_load_lds_dwordx4 refills while the tile is evaluated) on a frame of three ragged strips
-    by twelve ragged steps; walks of twelve, six and one step (MAGICKHIP_STRIP_CUTS).
-    Bit-identical to the reference and to the tile kernel."""
+def test_symmetric_convex_kernels_over_three_ragged_tile_columns(im, refmod, method, kernel, channels):
+    """The union-of-rectangles evaluation (morph_rects_kernel) on a tall frame of three tile columns by twelve tile
+    rows, ragged at the right and bottom edges.  Bit-identical to the reference."""
     import bench
-    options.set("MAGICKHIP_STRIPS", "1")
-    if cuts is not None:
-        options.set("MAGICKHIP_STRIP_CUTS", str(cuts))
     px = make_pixels(271, 530, channels, Q16, seed=len(kernel) + channels)
     dev, ref = run_pair(im, refmod, px)
     holder = {}
     launched = set(bench.kernel_profile(
         im, lambda: holder.update(out=im.morphology_image(dev, method, 1, kernel)), 1))
     assert launched == {"morph_rects"}, launched
-    got = holder["out"].numpy()
-    options.set("MAGICKHIP_STRIPS", None)
-    tiles = im.morphology_image(dev, method, 1, kernel).numpy()
-    assert np.array_equal(got, tiles), "%s %s c%d: strip walk != tile kernel at %s" % (
-        method, kernel, channels, np.argwhere(got != tiles)[:4].tolist())
-    if cuts in (1, None):
-        assert_parity(got, ref.morphology(method, 1, kernel).numpy(), True, "%s %s c%d" % (method, kernel, channels))
+    assert_parity(holder["out"].numpy(), ref.morphology(method, 1, kernel).numpy(), True,
+                  "%s %s c%d" % (method, kernel, channels))
 
 
-def test_strip_walk_channel_mask_and_change_count(im, refmod, options):
-    """morph_strips_kernel's general epilogue: channels without the update trait, the `changed`
-    count that ends an unbounded iteration, and a kernel whose origin is off centre."""
-    options.set("MAGICKHIP_STRIPS", "1")
-    options.set("MAGICKHIP_STRIP_CUTS", "2")
+def test_symmetric_convex_kernel_mask_count_and_off_centre_origin_over_several_tiles(im, refmod):
+    """morph_rects_kernel's general epilogue on frames of several tiles: channels without the update trait, the
+    `changed` count that ends an iterated Dilate, and a kernel whose origin is off centre."""
     px = make_pixels(200, 470, 4, Q16, seed=78)
     dev = im.Image(to_device(px), copy_channels=(1, 3))
     ref = refmod.RefImage(px).set_channel_mask("RB")

@@ -26,7 +26,7 @@ LABELS = [
     (r"blur_fused_exact_kernel<\d+, \d+, true, true>", "unsharp_fused_exact"),
     (r"blur_fused_exact_kernel<\d+, \d+, false, true>", "blur_fused_exact"),
     (r"conv2d_exact_kernel", "conv2d_exact"), (r"conv2d_tie", "conv2d_tie"),
-    (r"stretch_apply", "apply_lut"), (r"stretch_", "build_lut"), (r"morph_strips", "morph_rects"),
+    (r"stretch_apply", "apply_lut"), (r"stretch_", "build_lut"),
     (r"conv_mfma_kernel<true", "conv_column"), (r"conv_mfma_kernel<false", "conv_row"),
     (r"conv_column_", "conv_column"), (r"conv_row_alpha_audit", "conv_row_alpha_audit"), (r"conv_row_", "conv_row"),
     (r"resize_vertical", "resize_vertical"), (r"resize_horizontal", "resize_horizontal"),
