@@ -8,7 +8,8 @@
 //   NegateImage :3940-4100      QuantumRange-q in the Quantum's own arithmetic; with `grayscale`
 //                               only pixels that IsPixelGray (pixel-accessor.h:561-578)
 //   SigmoidalContrastImage :4267-4407   tanh form (MAGICKCORE_HAVE_ATANH); Sigmoidal(a,b,0) and
-//                               Sigmoidal(a,b,1) are formed on the host and passed in
+//                               Sigmoidal(a,b,1) are formed on the host and passed in; float samples at the
+//                               curve's zero are the host's (LevelsDoubt, mh_internal.hpp)
 //   GetImageRange statistic.c:1851-1929   per channel minimum and maximum, and those of column 0 of
 //                               channel 0 (every row is seeded with p[0], whatever the mask)
 //
@@ -95,7 +96,8 @@ static __device__ __forceinline__ Q levels_sample(const LevelsParams &p,Q q)
     {
       // ScaledSigmoidal, enhance.c:4207, :4228-4230: p.a = 0.5*contrast, p.b = QuantumScale*midpoint,
       // p.c = Sigmoidal(0), p.d = Sigmoidal(1)
-      const double s=tanh(p.a*(kQS*pixel-p.b));
+      // (a sample of exactly 0 is Sigmoidal(0) itself: the host's value, so the difference is the reference's 0)
+      const double s=pixel == 0.0 ? p.c : tanh(p.a*(kQS*pixel-p.b));
       return QuantumOps<Q>::clamp(kQR*((s-p.c)/(p.d-p.c)));
     }
   else if constexpr (MODE == MH_LEVELS_SIGMOIDAL_INVERSE)
@@ -103,7 +105,8 @@ static __device__ __forceinline__ Q levels_sample(const LevelsParams &p,Q q)
       // InverseScaledSigmoidal, enhance.c:4240-4256: p.a = 2.0/contrast
       const double argument=(p.d-p.c)*(kQS*pixel)+p.c;
       const double clamped=argument < -1+kEps ? -1+kEps : (argument > 1-kEps ? 1-kEps : argument);
-      return QuantumOps<Q>::clamp(kQR*(p.b+p.a*atanh(clamped)));
+      // (a sample of exactly 0: the argument is p.c, and p.e the host's atanh of it)
+      return QuantumOps<Q>::clamp(kQR*(p.b+p.a*(pixel == 0.0 ? p.e : atanh(clamped))));
     }
   else
     {
@@ -131,6 +134,14 @@ static __device__ __forceinline__ bool levels_pixel_gray(const Q (&q)[C],int col
     }
 }
 
+// a sample the host evaluates: not 0 (that one is exact), below p.doubt in magnitude (a NaN is not)
+template<typename Q>
+static __device__ __forceinline__ bool levels_doubtful(const LevelsParams &p,Q q)
+{
+  const double v=(double) q;
+  return (v != 0.0) && (fabs(v) < p.doubt);
+}
+
 template<typename Q,int C,int MODE>
 static __device__ __forceinline__ void levels_point_loop(const LevelsPointArgs &a)
 {
@@ -146,9 +157,54 @@ static __device__ __forceinline__ void levels_point_loop(const LevelsPointArgs &
 #pragma unroll
       for (int c=0; c < C; c++)
         if (((a.p.update_mask >> c) & 1u) != 0)
-          q[c]=levels_sample<Q,MODE>(a.p,q[c]);
+          {
+            if constexpr (QuantumOps<Q>::is_float && ((MODE == MH_LEVELS_SIGMOIDAL) || (MODE == MH_LEVELS_SIGMOIDAL_INVERSE)))
+              if ((a.p.doubt_list != nullptr) && levels_doubtful(a.p,q[c]))
+                {
+                  // the host's libm decides this one (launch_levels_scatter); what is stored below is overwritten
+                  const unsigned long long slot=atomicAdd(a.p.doubt_count,1ull);
+                  if (slot < a.p.doubt_capacity)
+                    {
+                      a.p.doubt_list[slot].index=i*C+(unsigned long long) c;
+                      a.p.doubt_list[slot].original=(float) q[c];
+                    }
+                }
+            q[c]=levels_sample<Q,MODE>(a.p,q[c]);
+          }
       store_pixel<Q,C>(pixels+i*C,q);
     }
+}
+
+// the doubtful samples of a float frame under a sigmoidal, counted before the point kernel records them
+template<typename Q,int C>
+__global__ __launch_bounds__(kLevelsThreads)
+void levels_doubt_count_kernel(LevelsPointArgs a)
+{
+  const Q *pixels=static_cast<const Q *>(a.pixels);
+  const unsigned long long stride=(unsigned long long) gridDim.x*kLevelsThreads;
+  unsigned long long n=0;
+  for (unsigned long long i=(unsigned long long) blockIdx.x*kLevelsThreads+threadIdx.x; i < a.count; i+=stride)
+    {
+      Q q[C];
+      load_pixel<Q,C>(pixels+i*C,q);
+#pragma unroll
+      for (int c=0; c < C; c++)
+        if ((((a.p.update_mask >> c) & 1u) != 0) && levels_doubtful(a.p,q[c]))
+          n++;
+    }
+  if (n != 0)
+    atomicAdd(a.p.doubt_count,n);
+}
+
+// the host's values of the doubtful samples, each to its place
+template<typename Q>
+__global__ __launch_bounds__(kLevelsThreads)
+void levels_scatter_kernel(Q *pixels,unsigned long long samples,const LevelsDoubt *list,unsigned long long count)
+{
+  const unsigned long long stride=(unsigned long long) gridDim.x*kLevelsThreads;
+  for (unsigned long long k=(unsigned long long) blockIdx.x*kLevelsThreads+threadIdx.x; k < count; k+=stride)
+    if (list[k].index < samples)
+      pixels[list[k].index]=(Q) list[k].value;
 }
 
 template<typename Q,int C>
@@ -294,6 +350,38 @@ MhStatus launch_levels_point(const View &img,const LevelsParams &params)
     MH_HIP(hipGetLastError());
     return MhStatus(MH_OK);
   });
+}
+
+MhStatus launch_levels_doubt_count(const View &img,const LevelsParams &params,unsigned long long *count_device)
+{
+  LevelsPointArgs a={};
+  a.pixels=img.pixels;
+  a.count=(unsigned long long) img.columns*(unsigned long long) img.rows;
+  a.p=params;
+  a.p.doubt_count=count_device;
+  const unsigned blocks=levels_grid((size_t) a.count,kLevelsRangeMaxBlocks);
+  return dispatch_layout(img.quantum,img.channels,[&](auto L) {
+    ProfileScope prof("levels_doubt_count",img.stream);
+    hipLaunchKernelGGL((levels_doubt_count_kernel<typename decltype(L)::Q,L.C>),dim3(blocks),dim3(kLevelsThreads),0,
+      img.stream,a);
+    MH_HIP(hipGetLastError());
+    return MhStatus(MH_OK);
+  });
+}
+
+MhStatus launch_levels_scatter(const View &img,const LevelsDoubt *list,unsigned long long count)
+{
+  if (count == 0)
+    return MH_OK;
+  if (img.quantum != MH_QUANTUM_F32)
+    return fail(MH_BAD_ARGUMENT,"levels: only a float frame has doubtful samples");
+  const unsigned long long samples=(unsigned long long) img.columns*(unsigned long long) img.rows*
+    (unsigned long long) img.channels;
+  ProfileScope prof("levels_scatter",img.stream);
+  hipLaunchKernelGGL((levels_scatter_kernel<float>),dim3(levels_grid((size_t) count,1024u)),dim3(kLevelsThreads),0,
+    img.stream,static_cast<float *>(img.pixels),samples,list,count);
+  MH_HIP(hipGetLastError());
+  return MH_OK;
 }
 
 MhStatus launch_levels_range(const View &img,bool column0_only,double *result_device)

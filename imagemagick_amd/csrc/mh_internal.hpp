@@ -469,14 +469,31 @@ MhStatus launch_adaptive_threshold(const View &src,const View &dst,size_t width,
 //   NEGATE             QuantumRange-q;  NEGATE_GRAY: only where IsPixelGray (colours: the colour channels)
 enum { MH_LEVELS_LEVEL=0,MH_LEVELS_LEVEL_POW=1,MH_LEVELS_LEVELIZE=2,MH_LEVELS_LEVELIZE_POW=3,MH_LEVELS_SIGMOIDAL=4,
   MH_LEVELS_SIGMOIDAL_INVERSE=5,MH_LEVELS_NEGATE=6,MH_LEVELS_NEGATE_GRAY=7 };
+//
+// The sigmoidals on float Quantum, near the curve's zero: tanh(...)-c and b+a*atanh(...) cancel to the last bits of the
+// libm, and the device's differs from the host's there.  A sample of exactly 0 takes the host's values (c; e =
+// atanh(clamp(c))); a sample other than 0 below `doubt` in magnitude is DOUBTFUL: the kernel records (sample index,
+// original) in doubt_list, the host evaluates the curve with the libm the reference links and
+// launch_levels_scatter stores the values.  launch_levels_doubt_count counts them beforehand, so the list fits.
+struct LevelsDoubt
+{
+  unsigned long long index;            // sample index: pixel*channels+channel
+  float original,value;
+};
 struct LevelsParams
 {
   int mode=MH_LEVELS_LEVEL;
   int colours=0;
   uint32_t update_mask=0;
   double a=0.0,b=0.0,c=0.0,d=0.0;
+  double e=0.0,doubt=0.0;
+  LevelsDoubt *doubt_list=nullptr;
+  unsigned long long *doubt_count=nullptr;
+  unsigned long long doubt_capacity=0;
 };
 MhStatus launch_levels_point(const View &img,const LevelsParams &params);
+MhStatus launch_levels_doubt_count(const View &img,const LevelsParams &params,unsigned long long *count_device);
+MhStatus launch_levels_scatter(const View &img,const LevelsDoubt *list,unsigned long long count);
 // GetImageRange's raw material: result_device[2c], [2c+1] = minimum and maximum of channel c (DBL_MAX and
 // -DBL_MAX for a channel the frame lacks), [2*MH_MAX_CHANNELS], [+1] = those of column 0 of channel 0, the
 // seed of every row.  column0_only: only the seed is scanned, the channels' slots are empty.

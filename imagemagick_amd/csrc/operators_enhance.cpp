@@ -1239,6 +1239,59 @@ MH_API MhStatus MagickHipNegateImage(MhImage *image,int grayscale)
   return io.img.commit();
 }
 
+// The magnitude below which a float sample is doubtful under a sigmoidal (mh_internal.hpp, LevelsDoubt).  Around a
+// sample of 0 the result r is r'(0)*q, and the libm's last bits are worth E = QuantumRange*2^-53/|sig1-sig0| of it
+// (sharpen) or QuantumRange*2^-53*|b| (inverse: b+a*atanh(...) with a*atanh(...) = -b at the zero).  A result is kept
+// from the device from 2^30*E on, where E is 2^-6 of a float's last place: |q| >= 2*2^30*E/|r'(0)|, the 2 for the
+// curvature.  r'(0) = a*(1-sig0^2)/(sig1-sig0) (sharpen), a*(sig1-sig0)/(1-sig0^2) (inverse); where the curve is
+// saturated at 0 (1-sig0^2 below 1e-4) the slope says nothing and every sample is the host's.
+static double sigmoidal_doubt(bool sharpen,const double *p)
+{
+  const double slack=1.0-p[2]*p[2],span=fabs(p[3]-p[2]);
+  if (!(slack > 1.0e-4) || !(span > 0.0))
+    return HUGE_VAL;
+  const double last=ldexp(kQuantumRange,-23);             // 2^30 * QuantumRange * 2^-53
+  if (sharpen)
+    return 2.0*(last/span)/(p[0]*slack/span);
+  return 2.0*(last*(fabs(p[1])+1.0e-3))/(p[0]*span/slack);
+}
+
+// A sigmoidal on a float frame: the point kernel, and the doubtful samples from the host's libm
+static MhStatus sigmoidal_float(const View &view,LevelsParams params,int curve,const double *p)
+{
+  if ((view.columns == 0) || (view.rows == 0) || (params.update_mask == 0))
+    return MH_OK;
+  params.doubt=sigmoidal_doubt(curve == LEVELS_TABLE_SIGMOIDAL,p);
+  Temp counters;
+  MH_TRY(counters.alloc(view.device,2*sizeof(unsigned long long),view.stream));
+  MH_HIP(hipMemsetAsync(counters.ptr,0,2*sizeof(unsigned long long),view.stream));
+  MH_TRY(launch_levels_doubt_count(view,params,counters.as<unsigned long long>()));
+  unsigned long long count=0;
+  MH_HIP(hipMemcpyAsync(&count,counters.ptr,sizeof(count),hipMemcpyDeviceToHost,view.stream));
+  MH_HIP(hipStreamSynchronize(view.stream));
+  if (count == 0)
+    return launch_levels_point(view,params);
+  Temp list;
+  MH_TRY(list.alloc(view.device,(size_t) count*sizeof(LevelsDoubt),view.stream));
+  params.doubt_list=list.as<LevelsDoubt>();
+  params.doubt_count=counters.as<unsigned long long>()+1;
+  params.doubt_capacity=count;
+  MH_TRY(launch_levels_point(view,params));
+  std::vector<LevelsDoubt> host((size_t) count);
+  unsigned long long recorded=0;
+  MH_HIP(hipMemcpyAsync(&recorded,counters.as<unsigned long long>()+1,sizeof(recorded),hipMemcpyDeviceToHost,view.stream));
+  MH_HIP(hipMemcpyAsync(host.data(),list.ptr,host.size()*sizeof(LevelsDoubt),hipMemcpyDeviceToHost,view.stream));
+  MH_HIP(hipStreamSynchronize(view.stream));
+  if (recorded != count)
+    return fail(MH_DEVICE_ERROR,"SigmoidalContrastImage: %llu doubtful samples counted, %llu recorded",count,recorded);
+  for (size_t k=0; k < host.size(); k++)
+    host[k].value=(float) clamp_to_quantum(levels_curve(curve,p,(double) host[k].original),MH_QUANTUM_F32);
+  MH_HIP(hipMemcpyAsync(list.ptr,host.data(),host.size()*sizeof(LevelsDoubt),hipMemcpyHostToDevice,view.stream));
+  MH_TRY(launch_levels_scatter(view,list.as<LevelsDoubt>(),count));
+  MH_HIP(hipStreamSynchronize(view.stream));             // `host` leaves with this call
+  return MH_OK;
+}
+
 MH_API MhStatus MagickHipSigmoidalContrastImage(MhImage *image,int sharpen,double contrast,double midpoint)
 {
   MH_TRY(check_image(image,"SigmoidalContrastImage"));
@@ -1264,7 +1317,9 @@ MH_API MhStatus MagickHipSigmoidalContrastImage(MhImage *image,int sharpen,doubl
       params.b=p[1];
       params.c=p[2];
       params.d=p[3];
-      MH_TRY(launch_levels_point(view,params));
+      const double clamped=sig0 < -1+kMagickEpsilon ? -1+kMagickEpsilon : (sig0 > 1-kMagickEpsilon ? 1-kMagickEpsilon : sig0);
+      params.e=atanh(clamped);
+      MH_TRY(sigmoidal_float(view,params,sharpen != 0 ? LEVELS_TABLE_SIGMOIDAL : LEVELS_TABLE_SIGMOIDAL_INVERSE,p));
     }
   return io.img.commit();
 }

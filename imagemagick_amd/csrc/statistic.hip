@@ -269,9 +269,13 @@ static __device__ __forceinline__ Q stat_extreme(const Q *t,int tile_w,int W,int
   {
     case ST_MINIMUM: r=lo; break;
     case ST_MAXIMUM: r=hi; break;
-    case ST_GRADIENT: r=fabs(hi-lo); break;
-    default: r=fabs((hi-lo)*perceptible_reciprocal(hi+lo)); break;        // ST_CONTRAST
+    case ST_GRADIENT: r=hi-lo; break;
+    default: r=(hi-lo)*perceptible_reciprocal(hi+lo); break;        // ST_CONTRAST
   }
+  // MagickAbsoluteValue (image-private.h:45) is a comparison, not fabs: -0.0 stays -0.0.  A float window of equal
+  // negative samples has the contrast 0.0*(1/(2*sample)) = -0.0
+  if (((type == ST_GRADIENT) || (type == ST_CONTRAST)) && (r < 0.0))
+    r=-r;
   return QuantumOps<Q>::clamp(r);
 }
 

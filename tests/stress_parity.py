@@ -15,15 +15,26 @@ import numpy as np
 import torch
 import imagemagick_amd as im
 from oracle import ref as refmod
+import statistic_oracle
+import edge_blur_oracle
+import kuwahara_oracle
+import clahe_oracle
+import threshold_oracle
+import levels_oracle
+import scale_oracle
+from test_gpu_adaptive_threshold import BIASES as ADAPTIVE_BIASES
+from test_gpu_levels import LIBM_SHARE, level_libm
 
 rng = np.random.default_rng(1)
 _ready = False
 
 
 def setup(seed=1):
-    """Load the library (once), pin the starting precision and reseed the case generator."""
+    """Load the library (once), pin the starting precision, reseed the case generator and restart the case counters."""
     global rng, _ready
     rng = np.random.default_rng(seed)
+    declined.clear()
+    drawn.clear()
     if not _ready:
         im.load()
         refmod.set_thread_limit(os.cpu_count() or 1)
@@ -140,8 +151,13 @@ def check(name, got, want, limit, detail):
 # every layout: gray, gray + alpha, RGB, RGBA, four plain channels, 16 the pointwise enhance operators (FunctionImage,
 # ContrastImage, ModulateImage, GrayscaleImage) with random parameters, colourspace and channel mask, 17 MotionBlurImage /
 # RotationalBlurImage on every layout, alpha kind and shapes from 1 to 600 per side, 18 LocalContrastImage / DespeckleImage /
-# WaveletDenoiseImage on shapes from 33 to 600 per side; 16 to 18 draw both Quantum types)
-NUMBER_OF_OPS = 19
+# WaveletDenoiseImage on shapes from 33 to 600 per side; 16 to 18 draw both Quantum types, 19 StatisticImage: every type, windows
+# from 0 to the LDS limit with the three rank routes' boundaries at a fixed share, 20 BilateralBlurImage / SelectiveBlurImage,
+# 21 KuwaharaImage, 22 CLAHEImage: the whole operator on Q16 sRGB frames and the core on Lab ones, 23 the six threshold operators,
+# AdaptiveThresholdImage over more than one strip and band included, 24 the ten level operators, 25 SampleImage / ScaleImage /
+# ThumbnailImage; 19 to 25 draw both Quantum types, both precision modes, host and device memory, every layout the operator's own
+# tests run and a channel mask in half the cases, and nothing in them may be declined)
+NUMBER_OF_OPS = 26
 
 # families 16 to 18: cases the library declined / cases run, per family.  A declined case passes only when the decline
 # condition stated in morphology.hip holds for it, and at most a quarter of a family's cases may be declined.
@@ -274,12 +290,550 @@ def run_enhance_case(case):
     return check(name, got, want, 1 if case["libm"] else 0, what)
 
 
+# ------------------------------------------------------------------------------------------------ families 19 to 25
+# Every draw_*_case below builds its whole case on the host (tests/test_stress_draws.py draws a few hundred of each without a
+# GPU); a case is inside the operator's stated domain, so run_domain_case counts a MagickHipError as a mismatch.
+LAYOUT_CHANNELS = {"gray": 1, "gray+alpha": 2, "rgb": 3, "rgba": 4, "plain4": 4}
+MASK_LETTERS = {1: "R", 2: "RA", 3: "RGB", 4: "RGBA"}                  # gray is the red channel (pixel.h:49-78)
+MASK_BITS = {"R": 0x1, "G": 0x2, "B": 0x4, "A": 0x10}
+# StatisticImage: the rank routes switch at W*H = 16 and 32 (launch_statistic); one case in three walks this table in
+# order with a rank type, so 15 / 16 / 17 and 31 / 32 / 33 all come within a dozen cases
+STATISTIC_ROUTE_WINDOWS = [(4, 4), (17, 1), (8, 4), (3, 11), (5, 3), (1, 31), (2, 8), (1, 17), (32, 1), (33, 1), (16, 1), (2, 16)]
+STATISTIC_WORK = 1.5e6              # samples x window cells of one case: the reference's CPU time stays at tens of milliseconds
+EDGE_BLUR_WORK = 6.0e6
+SELECTIVE_INTENSITIES = [None, "Average", "Rec709Luminance", "Brightness"]      # test_selective_image_settings
+KUWAHARA_RADII = [0, 0.5, 1, 1.5, 2, 3, 4, 5, 7]
+CLAHE_BINS = [0, 2, 3, 64, 128, 255, 256, 300]
+CLAHE_CLIPS = [0.5, 1.0, 1.5, 2.0, 4.0, 1e6]
+THRESHOLD_OPERATORS = ["bilevel", "black", "white", "range", "auto", "adaptive"]
+COLOUR_LAYOUTS = ["rgb", "rgba", "plain4"]                            # Black / White / Range decline a gray frame
+ADAPTIVE_SPAN, ADAPTIVE_BAND_ROWS, ADAPTIVE_MAX_WIDTH = 512, 64, 257   # threshold.hip; test_stress_draws.py reads them there
+LEVEL_OPERATORS = ["level", "levelize", "gamma", "negate", "sigmoidal", "auto_level", "linear_stretch", "normalize",
+                   "brightness_contrast", "min_max_stretch"]
+SCALE_OPERATORS = ["sample", "scale", "thumbnail"]
+
+
+def statistic_fits(statistic, width, height, is_float):
+    """launch_statistic's LDS limit: the staged window of one channel."""
+    element = 2 if statistic in statistic_oracle.RANK or not is_float else 4
+    return (max(width, 1) + 15) * (max(height, 1) + 15) * element <= 65536
+
+
+def sample_offsets_fit(source, destination, percent):
+    """SampleImage's offset table stays inside the frame (the library declines the rest: the reference then reads
+    virtual pixels)."""
+    return int(scale_oracle.sample_offsets(source, destination, percent).max()) < source
+
+
+def new_case(op, layouts):
+    """What every case of families 19 to 25 draws first: the Quantum type, the precision mode, the memory kind, the layout and
+    the alpha kind of pixels / float_pixels."""
+    layout = layouts[int(rng.integers(0, len(layouts)))]
+    drawn[op] = drawn.get(op, 0) + 1
+    return {"op": op, "index": drawn[op] - 1, "float": bool(rng.random() < 0.5), "fast": bool(rng.random() < 0.5),
+            "host": bool(rng.random() < 0.2), "layout": layout, "channels": LAYOUT_CHANNELS[layout],
+            "kind": int(rng.integers(0, 6)), "mask": None, "copy": (), "bits": None, "colorspace": "sRGB", "intensity": None,
+            "source": "kind"}
+
+
+def draw_mask(case):
+    """A channel mask in half the cases, drawn as family 16 draws it (four plain channels keep the default mask, as in the
+    operators' own tests); the channels left out are copy channels."""
+    if case["layout"] != "plain4" and rng.random() < 0.5:
+        channels = case["channels"]
+        letters = MASK_LETTERS[channels]
+        keep = [c for c in range(channels) if rng.random() < 0.5] or [int(rng.integers(0, channels))]
+        case.update(mask="".join(letters[c] for c in keep), copy=tuple(c for c in range(channels) if c not in keep),
+                    bits=sum(MASK_BITS[letters[c]] for c in keep))
+
+
+def draw_sides(most_rows, most_cols):
+    """Frame sides from 1 up; one case in five is thin (one side 1 to 3)."""
+    rows, cols = int(rng.integers(1, most_rows + 1)), int(rng.integers(1, most_cols + 1))
+    if rng.random() < 0.2:
+        thin = int(rng.integers(1, 4))
+        rows, cols = (thin, cols) if rng.random() < 0.5 else (rows, thin)
+    return rows, cols
+
+
+def shrink_to_work(rows, cols, per_pixel, most):
+    """Halves the longer side until rows x cols x per_pixel fits `most`."""
+    while rows * cols * per_pixel > most and max(rows, cols) > 1:
+        rows, cols = (max(rows // 2, 1), cols) if rows >= cols else (rows, max(cols // 2, 1))
+    return rows, cols
+
+
+def new_seed():
+    return int(rng.integers(0, 1 << 30))
+
+
+def smooth_frame(rows, cols, channels, is_float):
+    """A ramp of 300 levels a column and 150 a row under 400 levels of noise: a SelectiveBlurImage threshold splits its windows."""
+    y, x = np.mgrid[0:rows, 0:cols]
+    base = (x * 300.0 + y * 150.0) % 60000.0
+    a = np.stack([base * (0.6 + 0.1 * c) + rng.integers(0, 400, (rows, cols)) for c in range(channels)], axis=2)
+    if is_float:
+        return np.ascontiguousarray((a + rng.random(a.shape)).astype(np.float32))
+    return np.ascontiguousarray(a.astype(np.uint16))
+
+
+def all_pixels_gray(frame):
+    """IsPixelGray (pixel-accessor.h:561-578) on every pixel of a frame with three colour channels."""
+    if frame.shape[2] < 3:
+        return False
+    p = frame[..., :3].astype(np.float64)
+    return bool(((np.abs(p[..., 0] - p[..., 1]) < 1.0e-12) & (np.abs(p[..., 1] - p[..., 2]) < 1.0e-12)).all())
+
+
+def gamma_draw():
+    """0, 1, or log-uniform over 0.1 ... 10."""
+    u = rng.random()
+    return 0.0 if u < 0.15 else 1.0 if u < 0.4 else float(10.0 ** rng.uniform(-1.0, 1.0))
+
+
+def draw_statistic_case(op=19):
+    case = new_case(op, ["gray", "gray+alpha", "rgb", "rgba"])
+    is_float, channels = case["float"], case["channels"]
+    while True:
+        statistic = list(statistic_oracle.TYPES)[int(rng.integers(0, len(statistic_oracle.TYPES)))]
+        u = rng.random()
+        if case["index"] % 3 == 0:
+            statistic = statistic_oracle.RANK[int(rng.integers(0, 3))]
+            width, height = STATISTIC_ROUTE_WINDOWS[(case["index"] // 3) % len(STATISTIC_ROUTE_WINDOWS)]
+        elif u < 0.05:                                 # up to the LDS limit: one side long, the other what still fits
+            width = int(rng.integers(41, 400))
+            height = int(rng.integers(1, max(2, 32768 // (width + 15) - 14)))
+            if rng.random() < 0.5:
+                width, height = height, width
+        elif u < 0.05 + 1.0 / 6.0:
+            width, height = int(rng.integers(13, 41)), int(rng.integers(13, 41))
+        else:
+            width, height = int(rng.integers(0, 13)), int(rng.integers(0, 13))
+        if statistic_fits(statistic, width, height, is_float):
+            break
+    rows, cols = shrink_to_work(*draw_sides(120, 160), channels * max(width, 1) * max(height, 1), STATISTIC_WORK)
+    if statistic in statistic_oracle.RANK and rng.random() < 1.0 / 3.0:
+        keys, seed = ["binary", "levels"][int(rng.integers(0, 2))], new_seed()
+        frame = statistic_oracle.repeated_keys(rows, cols, channels, np.float32 if is_float else np.uint16, keys, seed)
+        case["source"] = "repeated_keys %s seed %d" % (keys, seed)
+    else:
+        frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+        if is_float:
+            if rng.random() < 1.0 / 3.0:
+                frame = rng.uniform(-3000.0, 70000.0, frame.shape).astype(np.float32)
+                case["source"] = "uniform -3000 ... 70000"
+            frame[rng.random(frame.shape) < 0.01] = np.nan
+    draw_mask(case)
+    case.update(name="statistic", args=(statistic, width, height), frame=np.ascontiguousarray(frame))
+    return case
+
+
+def draw_edge_blur_case(op=20):
+    case = new_case(op, ["gray", "gray+alpha", "rgb", "rgba"])
+    is_float, channels = case["float"], case["channels"]
+    dtype = np.float32 if is_float else np.uint16
+    if rng.random() < 0.5:
+        def side():                                    # odd, 0 meaning 1
+            u = rng.random()
+            return 0 if u < 0.1 else 2 * int(rng.integers(0, 8 if u > 0.1 + 1.0 / 6.0 else 17)) + 1
+        width, height = side(), side()
+        rows, cols = shrink_to_work(*draw_sides(100, 140), channels * max(width, 1) * max(height, 1), EDGE_BLUR_WORK)
+        high, seed = (70000 if is_float and rng.random() < 1.0 / 3.0 else 65535), new_seed()
+        # samples from 300 up only: the reference never writes the table slot a zero intensity byte reads (edge_blur_oracle)
+        frame = edge_blur_oracle.bilateral_pixels(rows, cols, channels, dtype, seed=seed, high=high)
+        case.update(name="bilateral_blur", args=(width, height, float(rng.uniform(1.0, 250.0)), float(rng.uniform(0.5, 12.0))),
+                    source="bilateral_pixels seed %d high %d" % (seed, high))
+    else:
+        if rng.random() < 0.5:
+            radius, sigma = 0.0, float(rng.uniform(0.5, 4.0))
+            reach = 8.0 * sigma + 3.0                  # no narrower than the width the reference takes from the sigma
+        else:
+            radius, sigma = float(rng.integers(1, 7)), float(rng.uniform(0.5, 4.0))
+            reach = 2.0 * radius + 1.0
+        u = rng.random()
+        threshold = 0.0 if u < 0.1 else 1e9 if u < 0.2 else float(10.0 ** rng.uniform(0.0, 5.0))
+        rows, cols = shrink_to_work(*draw_sides(100, 140), channels * reach * reach, EDGE_BLUR_WORK)
+        if rng.random() < 0.5:
+            frame = smooth_frame(rows, cols, channels, is_float)
+            if channels in (2, 4):                     # ... with the alpha of the drawn kind, a sprite's included
+                frame[..., -1] = enhance_frame(rows, cols, 4, is_float, case["kind"])[..., 3]
+            case["source"] = "smooth"
+        else:
+            frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+        if channels >= 3:
+            case.update(intensity=SELECTIVE_INTENSITIES[int(rng.integers(0, len(SELECTIVE_INTENSITIES)))],
+                        colorspace=["sRGB", "RGB"][int(rng.integers(0, 2))])
+        case.update(name="selective_blur", args=(radius, sigma, threshold))
+    draw_mask(case)
+    case["frame"] = np.ascontiguousarray(frame)
+    return case
+
+
+def draw_kuwahara_case(op=21):
+    case = new_case(op, kuwahara_oracle.LAYOUTS)
+    is_float, channels = case["float"], case["channels"]
+    radius = float(rng.integers(8, 16)) if rng.random() < 0.1 else float(KUWAHARA_RADII[int(rng.integers(0, len(KUWAHARA_RADII)))])
+    rows, cols = draw_sides(100, 140)
+    frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+    if is_float and rng.random() < 1.0 / 3.0:
+        which, seed = ["wide_range_float", "out_of_range_float"][int(rng.integers(0, 2))], new_seed()
+        frame = getattr(kuwahara_oracle, which)(rows, cols, channels, seed=seed)
+        case["source"] = "%s seed %d" % (which, seed)
+    if case["layout"] in ("gray+alpha", "rgba") and rng.random() < 1.0 / 3.0:
+        seed = new_seed()
+        frame = kuwahara_oracle.sprite_alpha(frame, fraction=0.6, seed=seed)
+        case["source"] += " sprite_alpha seed %d" % seed
+    draw_mask(case)
+    case.update(name="kuwahara", args=(radius, float(rng.uniform(0.3, 3.5))), frame=np.ascontiguousarray(frame))
+    return case
+
+
+def draw_clahe_case(op=22):
+    case = new_case(op, ["rgb", "rgba"])
+    is_float, channels = case["float"], case["channels"]
+    dtype = np.float32 if is_float else np.uint16
+    rows, cols = int(rng.integers(16, 201)), int(rng.integers(16, 261))      # (automatic tiles are an eighth of a side)
+    while True:
+        width, height = (0 if rng.random() < 0.2 else int(rng.integers(2, 65)) for _ in range(2))
+        bins = CLAHE_BINS[int(rng.integers(0, len(CLAHE_BINS)))]
+        if clahe_oracle.table_fits(rows, cols, channels, dtype, width, height, bins):
+            break
+    clip = CLAHE_CLIPS[int(rng.integers(0, len(CLAHE_CLIPS)))] if rng.random() < 0.5 else float(rng.uniform(0.1, 8.0))
+    # Q16: the whole operator from sRGB or the core on a frame declared Lab; float Quantum: the core only (from sRGB the
+    # contract is "equals the device's own chain", README: CLAHEImage, and stays with test_gpu_clahe.py)
+    case["colorspace"] = "Lab" if is_float or rng.random() < 0.5 else "sRGB"
+    u = rng.random()
+    if is_float and u < 0.25:
+        seed = new_seed()
+        frame, case["source"] = clahe_oracle.float_specials(rows, cols, channels, seed=seed), "float_specials seed %d" % seed
+    elif u < 0.6:
+        which = sorted(clahe_oracle.INPUTS)[int(rng.integers(0, len(clahe_oracle.INPUTS)))]
+        frame, case["source"] = clahe_oracle.INPUTS[which](rows, cols, channels, dtype), which
+    else:
+        frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+    draw_mask(case)
+    case.update(name="clahe", args=(width, height, bins, clip), frame=np.ascontiguousarray(frame))
+    return case
+
+
+def draw_threshold_case(op=23):
+    case = new_case(op, threshold_oracle.LAYOUTS)
+    which = THRESHOLD_OPERATORS[case["index"] % len(THRESHOLD_OPERATORS)]      # equal shares
+    if which in ("black", "white", "range") and case["layout"] not in COLOUR_LAYOUTS:
+        case["layout"] = COLOUR_LAYOUTS[int(rng.integers(0, len(COLOUR_LAYOUTS)))]
+    if which in ("bilevel", "auto") and rng.random() < 0.35:      # an intensity method of its own, on a colour frame
+        names = list(threshold_oracle.INTENSITIES)
+        case.update(intensity=names[int(rng.integers(0, len(names)))], colorspace=["sRGB", "RGB"][int(rng.integers(0, 2))],
+                    layout=["rgb", "rgba"][int(rng.integers(0, 2))])
+    case["channels"] = LAYOUT_CHANNELS[case["layout"]]
+    channels = case["channels"]
+    if which == "adaptive":
+        ordinal = case["index"] // len(THRESHOLD_OPERATORS)
+        shape = {1: "strip", 3: "band"}.get(ordinal % 10, "plain")      # one adaptive case in ten each, on Q16
+        if shape != "plain":
+            case["float"] = False
+        is_float = case["float"]
+        width = int(rng.integers(41, ADAPTIVE_MAX_WIDTH + 1)) if not is_float and rng.random() < 0.125 else int(rng.integers(0, 41))
+        height = int(rng.integers(41, 151)) if rng.random() < 0.125 else int(rng.integers(0, 41))
+        rows, cols = draw_sides(140, 200)
+        if shape == "strip":                           # more columns than one strip keeps: 512-(W-1)
+            rows, cols = min(rows, 24), ADAPTIVE_SPAN - (max(width, 1) - 1) + int(rng.integers(1, 60))
+        elif shape == "band":                          # more rows than one band: max(64, 4H)
+            rows, cols = max(ADAPTIVE_BAND_ROWS, 4 * height) + int(rng.integers(1, 40)), min(cols, 40)
+        bias = float(ADAPTIVE_BIASES[int(rng.integers(0, len(ADAPTIVE_BIASES)))]) if rng.random() < 0.5 else float(rng.uniform(-3000.0, 3000.0))
+        if is_float and rng.random() < 1.0 / 3.0:      # the running sum carries its rounding along the row
+            seed = new_seed()
+            frame, case["source"] = kuwahara_oracle.wide_range_float(rows, cols, channels, seed=seed), "wide_range_float seed %d" % seed
+        else:
+            frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+        case.update(name="adaptive", args=(width, height, bias), shape=shape)
+    else:
+        is_float = case["float"]
+        dtype = np.float32 if is_float else np.uint16
+        rows, cols = draw_sides(140, 200)
+        u = rng.random()
+        if u < 0.125:
+            frame, case["source"] = threshold_oracle.constant(rows, cols, channels, dtype), "constant"
+        elif u < 0.25:
+            seed = new_seed()
+            frame, case["source"] = threshold_oracle.two_level(rows, cols, channels, dtype, seed=seed), "two_level seed %d" % seed
+        else:
+            frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+
+        def level():                                   # a quarter exactly on a sample of the frame: the < / <= edges
+            if rng.random() < 0.25:
+                return float(frame[int(rng.integers(0, rows)), int(rng.integers(0, cols)), int(rng.integers(0, channels))])
+            return float(rng.uniform(-1000.0, 67000.0))
+        if which == "bilevel":
+            args = (level(),)
+        elif which in ("black", "white"):
+            args = (tuple(level() for _ in range(channels)),)
+        elif which == "range":
+            args = tuple(sorted(level() for _ in range(4)))
+        else:
+            args = (list(threshold_oracle.METHODS)[int(rng.integers(0, len(threshold_oracle.METHODS)))],)
+        case.update(name=which, args=args)
+    draw_mask(case)
+    case["frame"] = np.ascontiguousarray(frame)
+    return case
+
+
+def draw_levels_case(op=24):
+    case = new_case(op, levels_oracle.LAYOUTS)
+    is_float, channels = case["float"], case["channels"]
+    which = LEVEL_OPERATORS[int(rng.integers(0, len(LEVEL_OPERATORS)))]
+    while True:
+        rows, cols = draw_sides(200, 260)
+        frame = enhance_frame(rows, cols, channels, is_float, case["kind"])
+        case["source"] = "kind"
+        if which in ("auto_level", "normalize", "min_max_stretch", "linear_stretch") and rng.random() < 0.5:
+            low, span = float(rng.uniform(0.0, 30000.0)), float(rng.uniform(0.0, 0.5))      # a range for the stretch to find
+            frame = (frame * span + low).astype(frame.dtype) if is_float else (frame * span + low).astype(np.uint16)
+            case["source"] = "kind x %.17g + %.17g" % (span, low)
+        if channels >= 3 and rng.random() < 0.25:
+            seed = new_seed()
+            frame = levels_oracle.gray_pixels(frame, seed=seed)
+            case["source"] += " gray_pixels seed %d" % seed
+        if which != "normalize" or not all_pixels_gray(frame):
+            break
+        # NormalizeImage is ContrastStretchImage, which hands a colour frame that IdentifyImageType would call gray back
+        # untouched (MagickHipContrastStretchImage, enhance.c:1586: the reference re-lays it out): another frame, another kind
+        case["kind"] = (case["kind"] + 1) % 6
+    libm = False
+    if which in ("level", "levelize"):
+        gamma = gamma_draw()
+        args = (float(rng.uniform(-5000.0, 70000.0)), float(rng.uniform(-5000.0, 70000.0)), gamma)
+        libm = level_libm(gamma) if which == "level" else gamma != 1.0
+    elif which == "gamma":
+        args = (gamma_draw(),)
+    elif which == "negate":
+        args = (bool(rng.random() < 0.5),)
+    elif which == "sigmoidal":
+        args, libm = (bool(rng.random() < 0.5), float(10.0 ** rng.uniform(-2.0, np.log10(20.0))), float(rng.uniform(-1000.0, 70000.0))), True
+    elif which == "linear_stretch":
+        args = (float(rng.uniform(0.0, rows * cols)), float(rng.uniform(0.0, rows * cols)))
+    elif which == "brightness_contrast":
+        args = (float(rng.uniform(-100.0, 100.0)), float(rng.uniform(-100.0, 100.0)))
+    elif which == "min_max_stretch":
+        gamma = gamma_draw()
+        args, libm = (float(rng.uniform(0.0, 2000.0)), float(rng.uniform(0.0, 2000.0)), gamma), gamma != 1.0
+    else:
+        args = ()
+    draw_mask(case)
+    case.update(name=which, args=args, libm=libm, frame=np.ascontiguousarray(frame))
+    return case
+
+
+def draw_scale_case(op=25):
+    case = new_case(op, scale_oracle.LAYOUTS)
+    which = SCALE_OPERATORS[int(rng.integers(0, len(SCALE_OPERATORS)))]
+    if which == "thumbnail" and case["layout"] not in ("rgb", "rgba"):      # the layouts test_thumbnail runs
+        case["layout"] = ["rgb", "rgba"][int(rng.integers(0, 2))]
+        case["channels"] = LAYOUT_CHANNELS[case["layout"]]
+    is_float, channels = case["float"], case["channels"]
+    dtype = np.float32 if is_float else np.uint16
+    offset = scale_oracle.SAMPLE_OFFSETS[int(rng.integers(0, len(scale_oracle.SAMPLE_OFFSETS)))] if which == "sample" else None
+    while True:
+        rows, cols = int(rng.integers(1, 301)), int(rng.integers(1, 301))
+        if rng.random() < 1.0 / 6.0:
+            rows, cols = (1, cols) if rng.random() < 0.5 else (rows, 1)
+        to_rows, to_cols = int(rng.integers(1, 401)), int(rng.integers(1, 401))
+        u = rng.random()
+        if u < 0.1:                                    # an integer factor exactly, either way
+            rows, cols = min(rows, 75), min(cols, 75)
+            fy, fx = int(rng.integers(1, 5)), int(rng.integers(1, 5))
+            if rng.random() < 0.5:
+                to_rows, to_cols = rows * fy, cols * fx
+            else:
+                to_rows, to_cols, rows, cols = rows, cols, rows * fy, cols * fx
+        elif u < 0.2:                                  # source and destination coprime
+            while np.gcd(rows, to_rows) != 1:
+                to_rows = to_rows % 400 + 1
+            while np.gcd(cols, to_cols) != 1:
+                to_cols = to_cols % 400 + 1
+        ox, oy = scale_oracle.offset_percent(offset)
+        if which != "sample" or (rows, cols) == (to_rows, to_cols) or \
+                (sample_offsets_fit(rows, to_rows, oy) and sample_offsets_fit(cols, to_cols, ox)):
+            break
+    transparent = [0.0, 0.2, 0.9][int(rng.integers(0, 3))]
+    seed = new_seed()
+    if is_float and scale_oracle.layout_has_alpha(case["layout"]) and rng.random() < 0.25:
+        frame, case["source"] = scale_oracle.negative_alpha_float(rows, cols, channels, seed=seed), "negative_alpha_float seed %d" % seed
+    else:
+        frame = scale_oracle.frame(case["layout"], rows, cols, dtype, seed=seed, transparent=transparent)
+        case["source"] = "frame seed %d transparent %g" % (seed, transparent)
+    draw_mask(case)
+    case.update(name=which, args=(to_rows, to_cols), offset=offset, frame=np.ascontiguousarray(frame))
+    return case
+
+
+DRAWS = {19: draw_statistic_case, 20: draw_edge_blur_case, 21: draw_kuwahara_case, 22: draw_clahe_case,
+         23: draw_threshold_case, 24: draw_levels_case, 25: draw_scale_case}
+
+
+def case_image(case, frame=None):
+    """The case's frame (a fresh copy: some operators work in place) as the library sees it."""
+    frame = case["frame"] if frame is None else frame
+    kw = {"colorspace": case["colorspace"], "has_alpha": case["layout"] in ("gray+alpha", "rgba"), "copy_channels": case["copy"]}
+    if case["bits"] is not None:
+        kw["channel_mask"] = case["bits"]
+    if case["intensity"] is not None:
+        kw["intensity"] = threshold_oracle.INTENSITIES[case["intensity"]]
+    if case["host"]:
+        return im.Image(frame.copy(), **kw)
+    return (dev_float if case["float"] else dev)(frame, **kw)
+
+
+def case_reference(case):
+    return threshold_oracle.ref_image(refmod, case["frame"], case["colorspace"], mask=case["mask"], intensity=case["intensity"])
+
+
+def describe(case):
+    frame = case["frame"]
+    return "#%d %s %s %dx%dx%d %s kind %d (%s) mask %s %s intensity %s %s %s" % (
+        case["index"], case["args"], frame.dtype.name, frame.shape[0], frame.shape[1], frame.shape[2], case["layout"], case["kind"],
+        case["source"], case["mask"], case["colorspace"], case["intensity"], "fast" if case["fast"] else "exact",
+        "host" if case["host"] else "device")
+
+
+def compare(name, got, want, what, libm=False, ulp=0, level=0):
+    """Bit-identical (float NaNs at the same places); ulp, level: what a float / a Q16 sample may be off; libm: float within
+    one ULP and, from 10 000 samples on, at most LIBM_SHARE of them different at all (test_gpu_levels.py)."""
+    if got.shape != want.shape:
+        print("MISMATCH %s %s: shape %s, reference %s" % (name, what, got.shape, want.shape), flush=True)
+        return 1
+    if want.dtype != np.float32:
+        return check(name, got, want, level, what)
+    if not libm:
+        return check_ulp(name, got, want, ulp, what) if ulp else check_bits(name, got, want, what)
+    if check_ulp(name, got, want, 1, what):
+        return 1
+    differ = ~((got.view(np.uint32) == want.view(np.uint32)) | np.isnan(want))
+    if want.size >= 10000 and differ.mean() > LIBM_SHARE:
+        print("MISMATCH %s %s: %.3g of the samples differ (at most %g)" % (name, what, differ.mean(), LIBM_SHARE), flush=True)
+        return 1
+    return 0
+
+
+def run_statistic(case, what):
+    got = im.statistic_image(case_image(case), *case["args"]).numpy()
+    want = statistic_oracle.ref_statistic(refmod, case_reference(case), *case["args"]).numpy()
+    return compare("statistic", got, want, what)
+
+
+def run_edge_blur(case, what):
+    if case["name"] == "bilateral_blur":
+        got = im.bilateral_blur_image(case_image(case), *case["args"]).numpy()
+        want = edge_blur_oracle.ref_bilateral(refmod, case_reference(case), *case["args"]).numpy()
+    else:
+        got = im.selective_blur_image(case_image(case), *case["args"]).numpy()
+        want = edge_blur_oracle.ref_selective(refmod, case_reference(case), *case["args"]).numpy()
+    return compare(case["name"], got, want, what)
+
+
+def run_kuwahara(case, what):
+    got = im.kuwahara_image(case_image(case), *case["args"]).numpy()
+    if case["layout"] == "plain4":
+        want = kuwahara_oracle.plain4_reference(refmod, case["frame"], *case["args"])
+    else:
+        want = kuwahara_oracle.ref_kuwahara(refmod, case_reference(case), *case["args"]).numpy()
+    return compare("kuwahara", got, want, what)
+
+
+def run_clahe(case, what):
+    got = im.clahe_image(case_image(case), *case["args"]).numpy()
+    want = clahe_oracle.ref_clahe(case_reference(case), *case["args"]).numpy()
+    return compare("clahe", got, want, what)
+
+
+def run_threshold(case, what):
+    name, args, image, ref = case["name"], case["args"], case_image(case), case_reference(case)
+    if name == "adaptive":
+        got = im.adaptive_threshold_image(image, *args).numpy()
+        want = threshold_oracle.ref_adaptive_threshold(refmod, ref, *args).numpy()
+    elif name == "bilevel":
+        got, want = im.bilevel_image(image, *args).numpy(), threshold_oracle.ref_bilevel(ref, *args).numpy()
+    elif name == "black":
+        got, want = im.black_threshold_image(image, args[0]).numpy(), threshold_oracle.ref_black_threshold(ref, args[0]).numpy()
+    elif name == "white":
+        got, want = im.white_threshold_image(image, args[0]).numpy(), threshold_oracle.ref_white_threshold(ref, args[0]).numpy()
+    elif name == "range":
+        got, want = im.range_threshold_image(image, *args).numpy(), threshold_oracle.ref_range_threshold(ref, *args).numpy()
+    else:
+        image, percent = im.auto_threshold_image(image, args[0])
+        ref, text = threshold_oracle.ref_auto_threshold(ref, args[0])
+        if "%g%%" % percent != text:
+            print("MISMATCH auto %s: threshold %g%%, reference %s" % (what, percent, text), flush=True)
+            return 1
+        got, want = image.numpy(), ref.numpy()
+    return compare(name, got, want, what)
+
+
+def run_levels(case, what):
+    name, args, image, ref = case["name"], case["args"], case_image(case), case_reference(case)
+    if name == "auto_level":
+        measured, expected = im.image_range(case_image(case)), levels_oracle.ref_range(case_reference(case))
+        if measured != expected:
+            print("MISMATCH auto_level %s: range %r, reference %r" % (what, measured, expected), flush=True)
+            return 1
+    if name == "linear_stretch":
+        image, black, white = im.linear_stretch_image(image, *args)
+        ref, text = levels_oracle.ref_linear_stretch(ref, *args)
+        if levels_oracle.linear_stretch_property(black, white) != text:
+            print("MISMATCH linear_stretch %s: bins %d, %d, reference %s" % (what, black, white, text), flush=True)
+            return 1
+    else:
+        image = {"level": im.level_image, "levelize": im.levelize_image, "gamma": im.gamma_image, "negate": im.negate_image,
+                 "sigmoidal": im.sigmoidal_contrast_image, "auto_level": im.auto_level_image, "normalize": im.normalize_image,
+                 "brightness_contrast": im.brightness_contrast_image, "min_max_stretch": im.min_max_stretch_image}[name](image, *args)
+        ref = {"level": levels_oracle.ref_level, "levelize": levels_oracle.ref_levelize, "gamma": levels_oracle.ref_gamma,
+               "negate": levels_oracle.ref_negate, "sigmoidal": levels_oracle.ref_sigmoidal, "auto_level": levels_oracle.ref_auto_level,
+               "normalize": levels_oracle.ref_normalize, "brightness_contrast": levels_oracle.ref_brightness_contrast,
+               "min_max_stretch": levels_oracle.ref_min_max_stretch}[name](ref, *args)
+    return compare(name, image.numpy(), ref.numpy(), what, libm=case["libm"])
+
+
+def run_scale(case, what):
+    name, (to_rows, to_cols), image, ref = case["name"], case["args"], case_image(case), case_reference(case)
+    what += " sample:offset %s" % case["offset"]
+    if name == "sample":
+        got = im.sample_image(image, to_cols, to_rows, None if case["offset"] is None else scale_oracle.offset_percent(case["offset"])).numpy()
+        want = scale_oracle.ref_sample(refmod, ref, to_rows, to_cols, case["offset"]).numpy()
+    elif name == "scale":
+        got, want = im.scale_image(image, to_cols, to_rows).numpy(), scale_oracle.ref_scale(refmod, ref, to_rows, to_cols).numpy()
+    else:
+        # ThumbnailImage keeps ResizeImage's contract: FAST within one level / one float ULP (test_gpu_scale.py, test_thumbnail)
+        got, want = im.thumbnail_image(image, to_cols, to_rows).numpy(), scale_oracle.ref_thumbnail(refmod, ref, to_rows, to_cols).numpy()
+        return compare(name, got, want, what, ulp=1 if case["fast"] else 0, level=1 if case["fast"] else 0)
+    return compare(name, got, want, what)
+
+
+RUNS = {19: run_statistic, 20: run_edge_blur, 21: run_kuwahara, 22: run_clahe, 23: run_threshold, 24: run_levels, 25: run_scale}
+
+
+def run_domain_case(case):
+    """Families 19 to 25 against the compiled reference, in the case's precision mode (restored afterwards)."""
+    what = describe(case)
+    im.set_precision(im.PRECISION_FAST if case["fast"] else im.PRECISION_EXACT)
+    try:
+        return RUNS[case["op"]](case, what)
+    except im.MagickHipError as error:
+        print("MISMATCH %s %s: declined inside the stated domain (%s)" % (case["name"], what, error), flush=True)
+        return 1
+    finally:
+        im.set_precision(im.PRECISION_EXACT)
+
+
 def run_case(op=None):
     """One random case of operator family `op` (None: any); returns the number of mismatches (0 or 1)."""
     failures = 0
+    if op is not None and op >= 19:                # (their draws start at the seed: test_stress_draws.py sees the same cases)
+        return run_domain_case(DRAWS[op](op))
     rows, cols, kind, px = draw_frame()
     if op is None:
         op = int(rng.integers(0, NUMBER_OF_OPS))
+    if op >= 19:
+        return run_domain_case(DRAWS[op](op))
     if op >= 16:
         return run_enhance_case(draw_enhance_case(op))
     detail = "%dx%d kind %d" % (rows, cols, kind)

@@ -107,6 +107,22 @@ def test_pointwise_odd_frames(im, refmod, layout, dtype):
         run_pointwise(im, refmod, out_of_range_float(37, 53, CHANNELS[layout]), "out of range %s" % layout, layout)
 
 
+def test_float_sigmoidal_on_samples_at_the_curve_s_zero(im, refmod):
+    """Reduced from stress family 24 (tests/stress_parity.py, seed 6024, cases #14, #84 and #1206): float alphas of
+    exactly 0 and of 1e-9 ... 1e-4 under both sigmoidals.  There sig(x) - sig(0), and b + (2/a) atanh(...) in the inverse
+    form, cancel to the last bits of tanh / atanh, where the device's libm and the host's differ: the device's results were
+    up to 2.6e-11 off, 7.6e8 float ULPs of a result that small (7.85e-12 where the reference keeps an alpha of 0.0).  A
+    sample of 0 now takes the host's constants and the other small ones the host's libm."""
+    px = frame("rgba", 8, 8, HDRI, seed=21)
+    px[..., 3] = (10.0 ** np.linspace(-9.0, -4.0, 64)).astype(np.float32).reshape(8, 8)
+    px[0, :4, 3] = 0.0
+    for sharpen, contrast, midpoint in [(1, 0.014478866124392493, 67587.2464210792), (1, 5.795376361120826, 15738.240882300885),
+                                        (0, 13.991473358900219, 27437.970158007392)]:
+        check(im.sigmoidal_contrast_image(device_image(im, px, "rgba"), sharpen, contrast, midpoint).numpy(),
+              ref_sigmoidal(ref_image(refmod, px), sharpen, contrast, midpoint).numpy(),
+              "sigmoidal %s, alpha 0 and 1e-9 ... 1e-4" % ((sharpen, contrast, midpoint),), True)
+
+
 @pytest.mark.parametrize("dtype", [Q16, HDRI])
 @pytest.mark.parametrize("mask", list(MASKS) + ["copy"])
 def test_channel_masks_and_a_copy_channel(im, refmod, mask, dtype):

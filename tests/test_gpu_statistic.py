@@ -77,6 +77,19 @@ def test_float_keys_outside_the_quantum_range(im, refmod):
             check(im, refmod, px, statistic, width, height, "wide float range")
 
 
+def test_contrast_of_equal_negative_samples_is_minus_zero(im, refmod):
+    """Reduced from stress family 19 (tests/stress_parity.py, seed 6019, case #604: Contrast, a 1 x 0 window, float
+    samples below 0).  MagickAbsoluteValue is `x < 0 ? -x : x`, so the contrast of a window of equal negative samples,
+    0.0 * (1 / (2 * sample)) = -0.0, keeps its sign; fabs gave +0.0."""
+    rng = np.random.default_rng(604)
+    px = rng.uniform(-3000.0, 70000.0, (9, 7, 2)).astype(np.float32)
+    px[2:5, 1:4] = np.float32(-1234.5)               # a 3 x 3 window of equal negative samples around (3, 2)
+    for width, height in [(1, 0), (1, 1), (3, 3)]:
+        got = check(im, refmod, px, "Contrast", width, height, "negative samples")
+        assert got[3, 2, 0] == 0 and np.signbit(got[3, 2, 0])
+        check(im, refmod, px, "Gradient", width, height, "negative samples")
+
+
 @pytest.mark.parametrize("dtype", [Q16, HDRI])
 def test_statistic_fast_precision_is_bit_identical(im, refmod, dtype):
     px = make_pixels(45, 70, 4, dtype, seed=31)
