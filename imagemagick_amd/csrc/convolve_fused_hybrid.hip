@@ -115,6 +115,63 @@ struct HybridGeometry
   static_assert((alpha_bytes % 16) == 0,"aligned planes");
 };
 
+// What a wave of the 16 does in the walk, from the geometry alone: a set of ROLE_* bits per wave index.  Waves with
+// the same set run the same walk (blur_fused_hybrid_kernel: walk), one compiled per set and entered through scalar
+// branches on the wave index BEFORE the loop, so no iteration tests a role.
+//   ROLE_STAGER  fetches and stages a 64th of the source window (waves 0 .. FETCH_GROUPS/64-1)
+//   ROLE_COLUMN  runs column tiles: the tile waves (neither stagers nor alpha waves), three tiles each, and, where
+//                that leaves tiles over, staging waves 0..3 behind their staging
+//   ROLE_ROW     runs one row tile (and its epilogue): every wave of four plain channels, waves 0..11 otherwise
+//   ROLE_ALPHA   runs the exact alpha chain: waves 12..15 of an alpha-weighted frame
+enum : unsigned { ROLE_STAGER=1u,ROLE_COLUMN=2u,ROLE_ROW=4u,ROLE_ALPHA=8u };
+
+template<int NC,int MODE>
+struct HybridRoles
+{
+  static constexpr bool BLEND=MODE == MFMA_BLEND4;
+  typedef HybridGeometry<NC,BLEND> G;
+  static constexpr int WAVES=16;
+  static constexpr int STAGERS=G::FETCH_GROUPS/64;
+  static constexpr int TILE_WAVES=WAVES-STAGERS-(BLEND ? 4 : 0);
+  static_assert(TILE_WAVES >= 1,"somebody runs the column pass");
+  static constexpr int CT=3;                   // column tiles in flight: what the registers hold
+  static constexpr int SPILLED=16 > CT*TILE_WAVES ? 16-CT*TILE_WAVES : 0;   // tiles the tile waves cannot take
+  static_assert(SPILLED <= 4*CT,"four staging waves take the rest");
+  static constexpr bool tile_wave(int wave) { return (wave >= STAGERS) && (wave < STAGERS+TILE_WAVES); }
+  static constexpr int spilled_tiles(int wave) { return SPILLED/4+(wave < SPILLED % 4 ? 1 : 0); }
+  static constexpr unsigned of(int wave)
+  {
+    return (wave < STAGERS ? ROLE_STAGER : 0u) |
+      (tile_wave(wave) || ((SPILLED > 0) && (wave < 4) && (spilled_tiles(wave) > 0)) ? ROLE_COLUMN : 0u) |
+      (!(BLEND || (MODE == MFMA_PLAIN3)) || (wave < 12) ? ROLE_ROW : 0u) |
+      (BLEND && (wave >= 12) ? ROLE_ALPHA : 0u);
+  }
+  // the first wave after `wave` with another set of roles (WAVES: none)
+  static constexpr int next(int wave)
+  {
+    int end=wave+1;
+    while ((end < WAVES) && (of(end) == of(wave)))
+      end++;
+    return end;
+  }
+};
+
+// walk(the roles of the calling wave), FIRST the first wave not dispatched yet
+template<class Roles,int FIRST,class Walk>
+static __device__ __forceinline__ void dispatch_roles(int wave,const Walk &walk)
+{
+  constexpr int END=Roles::next(FIRST);
+  if constexpr (END >= Roles::WAVES)
+    walk(std::integral_constant<unsigned,Roles::of(FIRST)>{});
+  else
+    {
+      if (wave < END)
+        walk(std::integral_constant<unsigned,Roles::of(FIRST)>{});
+      else
+        dispatch_roles<Roles,END>(wave,walk);
+    }
+}
+
 // Diagnostic build only (-DMH_HYBRID_TRACE, tools/trace_hybrid_blur.py): every wave of the first four
 // workgroups stamps the shader clock at the phase boundaries of 48 steady-state iterations:
 // trace[block][wave][iteration][mark].
@@ -315,8 +372,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // them and the other loop-invariant indices in registers: the kernel sits at the 128 registers
   // of a wave, and what the compiler spills it reloads from scratch INSIDE the walk, each reload
   // behind an s_waitcnt vmcnt(0) that also waits for the prefetched pixels: 9 such reloads cost
-  // 0.25 ms per 8192^2 frame.)
-  const bool stager=tid < G::FETCH_GROUPS;     // wave-uniform (FETCH_GROUPS is a multiple of 64)
+  // 0.25 ms per 8192^2 frame.)  Both lambdas are called from the staging waves' walks only.
   // An EDGE item: its staged window hangs over the image's left or right edge (the first and the last strip, every
   // segment of them), so some of its column groups are clamped.  Decided per ITEM — workgroup-uniform, a scalar
   // branch — and not per lane: a stager is thread tid/GROUPS_PER_ROW's row, so every staging wave of an edge item
@@ -329,48 +385,45 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   const bool edge_item=(xin0 < 0) || (xin0+4*G::GROUPS_PER_ROW > W);
   auto fetch=[&](int g,int srow,int sxg)
   {
-    if (stager)
+    int y=in0+G::GROUP*g+srow;
+    y=y < 0 ? 0 : (y > H-1 ? H-1 : y);       // the intermediate's edge clamp (cache.c:2663-2679)
+    const int xs=xin0+4*sxg;
+    if (__builtin_expect(!edge_item,1))
       {
-        int y=in0+G::GROUP*g+srow;
-        y=y < 0 ? 0 : (y > H-1 ? H-1 : y);       // the intermediate's edge clamp (cache.c:2663-2679)
-        const int xs=xin0+4*sxg;
-        if (__builtin_expect(!edge_item,1))
+        if constexpr (MODE == MFMA_PLAIN3)
           {
-            if constexpr (MODE == MFMA_PLAIN3)
-              {
-                // four RGB pixels = 24 contiguous bytes, re-cut into pixels
-                const uint16_t *at=args.src+pixel_index(y,W,xs)*3;
-                const LooseDword *words=reinterpret_cast<const LooseDword *>(at);
-                const uint2 a=make_uint2(words[0],words[1]),b=make_uint2(words[2],words[3]),c=make_uint2(words[4],words[5]);
-                raw[0]=make_uint2(a.x,a.y & 0xffffu);
-                raw[1]=make_uint2((a.y >> 16) | (b.x << 16),b.x >> 16);
-                raw[2]=make_uint2(b.y,c.x & 0xffffu);
-                raw[3]=make_uint2((c.x >> 16) | (c.y << 16),c.y >> 16);
-              }
-            else
-              {
-                typedef unsigned LooseQuad __attribute__((ext_vector_type(4),aligned(8)));
-                const LooseQuad *at=reinterpret_cast<const LooseQuad *>(args.src+pixel_index(y,W,xs)*4);
-                const LooseQuad a=at[0],b=at[1];
-                raw[0]=make_uint2(a[0],a[1]);
-                raw[1]=make_uint2(a[2],a[3]);
-                raw[2]=make_uint2(b[0],b[1]);
-                raw[3]=make_uint2(b[2],b[3]);
-              }
+            // four RGB pixels = 24 contiguous bytes, re-cut into pixels
+            const uint16_t *at=args.src+pixel_index(y,W,xs)*3;
+            const LooseDword *words=reinterpret_cast<const LooseDword *>(at);
+            const uint2 a=make_uint2(words[0],words[1]),b=make_uint2(words[2],words[3]),c=make_uint2(words[4],words[5]);
+            raw[0]=make_uint2(a.x,a.y & 0xffffu);
+            raw[1]=make_uint2((a.y >> 16) | (b.x << 16),b.x >> 16);
+            raw[2]=make_uint2(b.y,c.x & 0xffffu);
+            raw[3]=make_uint2((c.x >> 16) | (c.y << 16),c.y >> 16);
           }
         else
           {
-            // (opaque to the optimiser so that the four clamped columns are not kept in registers across the whole
-            // walk)
-            int edge=xs;
-            asm volatile("" : "+v"(edge));
+            typedef unsigned LooseQuad __attribute__((ext_vector_type(4),aligned(8)));
+            const LooseQuad *at=reinterpret_cast<const LooseQuad *>(args.src+pixel_index(y,W,xs)*4);
+            const LooseQuad a=at[0],b=at[1];
+            raw[0]=make_uint2(a[0],a[1]);
+            raw[1]=make_uint2(a[2],a[3]);
+            raw[2]=make_uint2(b[0],b[1]);
+            raw[3]=make_uint2(b[2],b[3]);
+          }
+      }
+    else
+      {
+        // (opaque to the optimiser so that the four clamped columns are not kept in registers across the whole
+        // walk)
+        int edge=xs;
+        asm volatile("" : "+v"(edge));
 #pragma unroll
-            for (int i=0; i < 4; i++)
-              {
-                int x=edge+i;
-                x=x < 0 ? 0 : (x > W-1 ? W-1 : x);
-                raw[i]=load_pixel16(args.src+pixel_index(y,W,x)*PX);
-              }
+        for (int i=0; i < 4; i++)
+          {
+            int x=edge+i;
+            x=x < 0 ? 0 : (x > W-1 ? W-1 : x);
+            raw[i]=load_pixel16(args.src+pixel_index(y,W,x)*PX);
           }
       }
   };
@@ -378,32 +431,29 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // a plain channel: hi/lo split) and, alpha-weighted frames, the alpha levels as two byte planes
   auto stage_group=[&](int srow,int sxg)
   {
-    if (stager)
-      {
-        f32x2 v[4][2];
-        quantum_to_samples<SAMPLES>(raw,v);
-        // (one address + immediate offsets)
-        unsigned char *to=smem_raw+G::ring_bytes+2*(srow*F::SR+4*sxg);
-        // (RGB frames: the fourth plane stays as it is — its row tiles are not run, what the column pass makes of it
-        // stays in the entries of the channel that is not stored)
-        constexpr int STAGED=MODE == MFMA_PLAIN3 ? 3 : G::STAGE_CHANNELS;
+    f32x2 v[4][2];
+    quantum_to_samples<SAMPLES>(raw,v);
+    // (one address + immediate offsets)
+    unsigned char *to=smem_raw+G::ring_bytes+2*(srow*F::SR+4*sxg);
+    // (RGB frames: the fourth plane stays as it is — its row tiles are not run, what the column pass makes of it
+    // stays in the entries of the channel that is not stored)
+    constexpr int STAGED=MODE == MFMA_PLAIN3 ? 3 : G::STAGE_CHANNELS;
 #pragma unroll
-        for (int c=0; c < STAGED; c++)
-          {
-            uint2 hi,lo;
-            split_f16_pair(v[c][0],hi.x,lo.x);
-            split_f16_pair(v[c][1],hi.y,lo.y);
-            *reinterpret_cast<uint2 *>(to+2*c*F::CHR)=hi;
-            *reinterpret_cast<uint2 *>(to+2*(G::STAGE_PLANE+c*F::CHR))=lo;
-          }
-        if constexpr (BLEND)
-          {
-            // bytes 2,3 of the second word of each pixel = the alpha level, paired over the four positions
-            const unsigned hy01=__builtin_amdgcn_perm(raw[1].y,raw[0].y,0x07030602u),hy23=__builtin_amdgcn_perm(raw[3].y,raw[2].y,0x07030602u);
-            unsigned char *line=smem_raw+G::ring_bytes+G::stage_bytes+srow*G::ASTRIDE+4*sxg;
-            *reinterpret_cast<unsigned *>(line)=__builtin_amdgcn_perm(hy23,hy01,0x05040100u) ^ 0x80808080u;
-            *reinterpret_cast<unsigned *>(line+G::GROUP*G::ASTRIDE)=__builtin_amdgcn_perm(hy23,hy01,0x07060302u) ^ 0x80808080u;
-          }
+    for (int c=0; c < STAGED; c++)
+      {
+        uint2 hi,lo;
+        split_f16_pair(v[c][0],hi.x,lo.x);
+        split_f16_pair(v[c][1],hi.y,lo.y);
+        *reinterpret_cast<uint2 *>(to+2*c*F::CHR)=hi;
+        *reinterpret_cast<uint2 *>(to+2*(G::STAGE_PLANE+c*F::CHR))=lo;
+      }
+    if constexpr (BLEND)
+      {
+        // bytes 2,3 of the second word of each pixel = the alpha level, paired over the four positions
+        const unsigned hy01=__builtin_amdgcn_perm(raw[1].y,raw[0].y,0x07030602u),hy23=__builtin_amdgcn_perm(raw[3].y,raw[2].y,0x07030602u);
+        unsigned char *line=smem_raw+G::ring_bytes+G::stage_bytes+srow*G::ASTRIDE+4*sxg;
+        *reinterpret_cast<unsigned *>(line)=__builtin_amdgcn_perm(hy23,hy01,0x05040100u) ^ 0x80808080u;
+        *reinterpret_cast<unsigned *>(line+G::GROUP*G::ASTRIDE)=__builtin_amdgcn_perm(hy23,hy01,0x07060302u) ^ 0x80808080u;
       }
   };
 
@@ -416,20 +466,18 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // tile on top of their chain.)  The 16 lanes of a read group are 16 rows, SR halves apart: 16 different
   // bank slots (alpha_plane_degree(2*SR) == 1).
   static_assert(alpha_plane_degree(2*F::SR) == 1,"the row operands' reads are conflict-free");
+  // (three channels: twelve row tiles — HybridRoles::of: ROLE_ROW)
   const int rc=wave >> 2,ot=wave & 3;
-  const bool row_wave=!(BLEND || (MODE == MFMA_PLAIN3)) || (wave < 12);   // wave-uniform (three channels: twelve row tiles)
   const int row_entry=rc*F::CHR+n*F::SR+16*ot+8*kq;
   // column pass: the sixteen tiles of a block belong to the waves that neither stage nor run the alpha tiles,
   // three at a time (the operands of three tiles in flight are what the registers hold).  Where that leaves
   // tiles over (81 taps, alpha-weighted: nine staging waves, four alpha waves, three tile waves = nine tiles) they
   // go to staging waves 0..3 — the oldest wave of each SIMD, served first, done with its staging after 1750 of
   // the interval's 2800 cycles — behind their staging.
-  constexpr int TILE_WAVES=16-G::FETCH_GROUPS/64-(BLEND ? 4 : 0);
-  static_assert(TILE_WAVES >= 1,"somebody runs the column pass");
-  constexpr int CT=3;
-  constexpr int SPILLED=16 > CT*TILE_WAVES ? 16-CT*TILE_WAVES : 0;   // tiles the tile waves cannot take
-  static_assert(SPILLED <= 4*CT,"four staging waves take the rest");
-  const int tile_wave=wave-G::FETCH_GROUPS/64; // < 0: a staging wave; >= TILE_WAVES: an alpha wave
+  typedef HybridRoles<NC,MODE> Roles;
+  constexpr int TILE_WAVES=Roles::TILE_WAVES,CT=Roles::CT,SPILLED=Roles::SPILLED;
+  const int tile_wave=wave-Roles::STAGERS;     // < 0: a staging wave; >= TILE_WAVES: an alpha wave
+  // (wave-uniform scalars; a wave without ROLE_COLUMN never reads them)
   int ctiles=0,ctile0=0;
   if ((tile_wave >= 0) && (tile_wave < TILE_WAVES))
     {
@@ -446,7 +494,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
     }
   else if ((SPILLED > 0) && (wave < 4))
     {
-      ctiles=SPILLED/4+(wave < SPILLED % 4 ? 1 : 0);
+      ctiles=Roles::spilled_tiles(wave);
       ctile0=CT*TILE_WAVES+wave*(SPILLED/4)+(wave < SPILLED % 4 ? wave : SPILLED % 4);
     }
   constexpr int GROUP_STRIDE=2*F::OB;          // f16 ring: halves per 16-row group
@@ -458,7 +506,6 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // the weights of rows 4*kq..+3 of column 16*t+n: 16 bytes, the four row quads of a column swizzled with the
   // column so that the 16 lanes of a b128 group (16 columns) fall into 16 different bank slots
   auto weight_slot=[&](int tile) { return (16*tile+n)*G::GROUP+4*(kq ^ ((n >> 2) & 3)); };
-  int ring_group=0;                            // g mod NR (wave-uniform)
   unsigned recomputed=0u;
 
   // ---- The walk.  Iteration g:
@@ -474,42 +521,63 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // (Rounds 4-5 ran the integer chain in interval B and carried its five class tiles across barrier Y: the
   // youngest waves of their SIMDs, the alpha waves issued their 18 matrix instructions behind the 27 of the row
   // waves, and the interval lasted until they were through.)
-  floatx4 sums_row={0.0f,0.0f,0.0f,0.0f};
-  intx4 plane_low={0,0,0,0},plane_high={0,0,0,0};
-  long plane_low2=0,plane_high2=0;
-  auto store_row=[&](int block,int lane)
+  //
+  // The walk is compiled once per set of roles (HybridRoles) and, in each, twice: the iterations
+  //   fill    g <= NG                     nothing to run the column pass on yet
+  //   steady  NG+1 <= g <= ngroups-2      (none when the item has fewer than four blocks)
+  //   drain   ngroups-1 <= g <= ngroups+1 nothing left to stage, then to fetch
+  // differ only in which of g < ngroups, g+1 < ngroups, 0 <= cb < nblocks and g >= 1 hold: all of them in the steady
+  // state, whose body (STEADY) tests none and stores whole rows (a block before the item's last lies inside the
+  // image).  Fill and drain share the body that tests them.  The bounds below are the same scalars for every role,
+  // and both barriers of an iteration stand in the one body every role is compiled from, outside the roles' code: a
+  // wave passes 2*walk_end barriers whatever it is.
+  const int steady_begin=G::NG+1;
+  const int steady_end=ngroups-1 > steady_begin ? ngroups-1 : steady_begin;
+  const int walk_end=ngroups+2;                  // > steady_end: the drain is never empty
+  auto walk=[&](auto roles) __attribute__((always_inline))
   {
-    if ((block >= 0) && (block < nblocks))
-      {
-        const uint2 result=out_tile[wave*G::OUT_STRIDE+lane];
-        const int x=x0+lane,y=out_begin+G::GROUP*block+wave;
-        if ((x < W) && (y < H))
-          store_pixel16(args.dst+pixel_index(y,W,x)*PX,result);
-      }
-  };
-  fetch(0,tid/G::GROUPS_PER_ROW,tid % G::GROUPS_PER_ROW);
-  // (s_setprio 3 for the alpha waves — the youngest waves of their SIMDs, with the longest chain of interval A —
-  // only changes who waits: 0.528 against 0.522 ms, profiles/r6_notes/hybrid_blur_steps.txt)
-  for (int g=0; g <= ngroups+1; g++)
+    constexpr unsigned ROLES=decltype(roles)::value;
+    constexpr bool STAGER=(ROLES & ROLE_STAGER) != 0u,COLUMN=(ROLES & ROLE_COLUMN) != 0u;
+    constexpr bool ROW=(ROLES & ROLE_ROW) != 0u,ALPHA=(ROLES & ROLE_ALPHA) != 0u;
+    static_assert(!ALPHA || (BLEND && !STAGER && !ROW && !COLUMN),"an alpha wave runs the integer chain only");
+    int ring_group=0;                            // g mod NR (wave-uniform)
+    // what crosses a barrier
+    floatx4 sums_row={0.0f,0.0f,0.0f,0.0f};      // ROW
+    intx4 plane_low={0,0,0,0},plane_high={0,0,0,0};   // ALPHA
+    long plane_low2=0,plane_high2=0;
+    if constexpr (STAGER)
+      fetch(0,tid/G::GROUPS_PER_ROW,tid % G::GROUPS_PER_ROW);
+    // (s_setprio 3 for the alpha waves — the youngest waves of their SIMDs, with the longest chain of interval A —
+    // only changes who waits: 0.528 against 0.522 ms, profiles/r6_notes/hybrid_blur_steps.txt)
+    auto iteration=[&](auto steady,const int g) __attribute__((always_inline))
     {
-      int opaque_tid=tid;
-      asm volatile("" : "+v"(opaque_tid));       // not loop-invariant to the optimiser (see `stager`)
-      const int srow=opaque_tid/G::GROUPS_PER_ROW,sxg=opaque_tid-srow*G::GROUPS_PER_ROW;
+      constexpr bool STEADY=decltype(steady)::value;
       const int cb=g-G::NG-1;                    // the column pass's block of this iteration
       const int first=ring_group;                // ring slot of group cb: (g-NG-1) mod NR = g mod NR
       const int previous=ring_group == 0 ? G::NR-1 : ring_group-1;   // ring slot of group g-1
-      MH_HTRACE_MARK(0);
-      if (g < ngroups)
+      // a stager's row and column group, not loop-invariant to the optimiser (see the staging lambdas); the other
+      // waves have neither
+      int opaque_tid=tid,srow=0,sxg=0;
+      if constexpr (STAGER)
         {
-          stage_group(srow,sxg);
+          asm volatile("" : "+v"(opaque_tid));
+          srow=opaque_tid/G::GROUPS_PER_ROW;
+          sxg=opaque_tid-srow*G::GROUPS_PER_ROW;
+        }
+      MH_HTRACE_MARK(0);
+      if (STEADY || (g < ngroups))
+        {
+          if constexpr (STAGER)
+            stage_group(srow,sxg);
           MH_HTRACE_MARK(1);
-          if (g+1 < ngroups)
-            fetch(g+1,srow,sxg);
+          if constexpr (STAGER)
+            if (STEADY || (g+1 < ngroups))
+              fetch(g+1,srow,sxg);
         }
       MH_HTRACE_MARK(2);
       // ======================================================================== interval A
       if constexpr (BLEND)
-        if (alpha_wave)
+        if constexpr (ALPHA)
           {
             // ---- the exact alpha sums of this wave's 16 x 16 tile of group g-1.  Sample = level*2^16: byte
             // planes 2 (low) and 3 (high); the products b_3 x d_j (class j) and b_2 x d_j (class j-1; b_2 x d_0
@@ -560,8 +628,17 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
                     level[r]=(unsigned) args.src[pixel_index(yy,W,xx)*4+3];
                   }
               };
-              recomputed+=settle_doubtful_pixels<false,4>(doubtful && (g >= 1) && (g-1 < ngroups) && (x < W),lane,
-                args.taps64,K,fetch_alpha,q);
+              // (the rare branch tests the lane masks themselves, as the scalars they are: the mask of each
+              // comparison, combined on the scalar side and opaque from there on.  The mask of the combined per-lane
+              // flag — or a branch on that flag, which `ballot != 0` is turned back into — goes through a vector
+              // register: a v_cndmask 0/1 and a v_cmp_ne in every iteration.)
+              unsigned long long todo=__builtin_amdgcn_ballot_w64(doubtful) & __builtin_amdgcn_ballot_w64(x < W);
+              if (!STEADY && !((g >= 1) && (g-1 < ngroups)))
+                todo=0ull;
+              asm volatile("" : "+s"(todo));
+              if (__builtin_expect(todo != 0ull,0))
+                recomputed+=settle_doubtful_pixels<false,4>(((todo >> lane) & 1ull) != 0ull,lane,args.taps64,K,
+                  fetch_alpha,q);
             }
             // the levels as the column pass's alpha samples (level/2: hi + lo is exact)
             const float half_level[4]={0.5f*(float) q[0],0.5f*(float) q[1],0.5f*(float) q[2],0.5f*(float) q[3]};
@@ -584,59 +661,64 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
           }
       MH_HTRACE_MARK(3);
       // ---- f16 column pass of block cb, whole (products, division, rounding) -> out_tile
-      if ((cb >= 0) && (cb < nblocks))
-        {
-          int chunk_at[NC];
-#pragma unroll
-          for (int c=0; c < NC; c++)
-            {
-              const unsigned wide=(unsigned) (first+2*c+(kq >> 1));
-              const unsigned group=wide < wide-(unsigned) G::NR ? wide : wide-(unsigned) G::NR;
-              chunk_at[c]=col_entry16+GROUP_STRIDE*(int) group;
-            }
-          auto column_tiles=[&](auto count,int done)
+      if constexpr (COLUMN)
+        if (STEADY || ((cb >= 0) && (cb < nblocks)))
           {
-            constexpr int N=decltype(count)::value;
-            floatx4 acc[N];
-#pragma unroll
-            for (int i=0; i < N; i++)
-              acc[i]=floatx4{0.0f,0.0f,0.0f,0.0f};
+            int chunk_at[NC];
 #pragma unroll
             for (int c=0; c < NC; c++)
               {
-                half8 a_hi[N],a_lo[N];
-#pragma unroll
-                for (int i=0; i < N; i++)
-                  {
-                    a_hi[i]=*reinterpret_cast<const half8 *>(ring_hi+chunk_at[c]+4*(done+i)*F::SC);
-                    a_lo[i]=*reinterpret_cast<const half8 *>(ring_lo+chunk_at[c]+4*(done+i)*F::SC);
-                  }
-#pragma unroll
-                for (int i=0; i < N; i++)
-                  acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi[i],toeplitz_hi(c),acc[i],0,0,0);
-#pragma unroll
-                for (int i=0; i < N; i++)
-                  acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo[i],toeplitz_hi(c),acc[i],0,0,0);
-#pragma unroll
-                for (int i=0; i < N; i++)
-                  acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi[i],toeplitz_lo(c),acc[i],0,0,0);
+                const unsigned wide=(unsigned) (first+2*c+(kq >> 1));
+                const unsigned group=wide < wide-(unsigned) G::NR ? wide : wide-(unsigned) G::NR;
+                chunk_at[c]=col_entry16+GROUP_STRIDE*(int) group;
               }
-#pragma unroll
-            for (int i=0; i < N; i++)
-              out_tile[n*G::OUT_STRIDE+4*(ctile0+done+i)+kq]=
-                sums_to_quantum<SAMPLES>(acc[i][0],acc[i][1],acc[i][2],acc[i][3],args.quantum_unit);
-          };
-          for (int done=0; done < ctiles; done+=CT)
+            auto column_tiles=[&](auto count,int done)
             {
-              const int left=ctiles-done;
-              if (left >= CT)
-                column_tiles(std::integral_constant<int,CT>{},done);
-              else if (left == 2)
-                column_tiles(std::integral_constant<int,2>{},done);
-              else
-                column_tiles(std::integral_constant<int,1>{},done);
-            }
-        }
+              constexpr int N=decltype(count)::value;
+              floatx4 acc[N];
+#pragma unroll
+              for (int i=0; i < N; i++)
+                acc[i]=floatx4{0.0f,0.0f,0.0f,0.0f};
+#pragma unroll
+              for (int c=0; c < NC; c++)
+                {
+                  half8 a_hi[N],a_lo[N];
+#pragma unroll
+                  for (int i=0; i < N; i++)
+                    {
+                      a_hi[i]=*reinterpret_cast<const half8 *>(ring_hi+chunk_at[c]+4*(done+i)*F::SC);
+                      a_lo[i]=*reinterpret_cast<const half8 *>(ring_lo+chunk_at[c]+4*(done+i)*F::SC);
+                    }
+#pragma unroll
+                  for (int i=0; i < N; i++)
+                    acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi[i],toeplitz_hi(c),acc[i],0,0,0);
+#pragma unroll
+                  for (int i=0; i < N; i++)
+                    acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo[i],toeplitz_hi(c),acc[i],0,0,0);
+#pragma unroll
+                  for (int i=0; i < N; i++)
+                    acc[i]=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi[i],toeplitz_lo(c),acc[i],0,0,0);
+                }
+#pragma unroll
+              for (int i=0; i < N; i++)
+                out_tile[n*G::OUT_STRIDE+4*(ctile0+done+i)+kq]=
+                  sums_to_quantum<SAMPLES>(acc[i][0],acc[i][1],acc[i][2],acc[i][3],args.quantum_unit);
+            };
+            // (a tile wave beside spilled tiles runs CT of them: known here, no test; else a wave-uniform count)
+            const int tiles=(!STAGER && (SPILLED > 0)) ? CT : ctiles;
+            // (the most any wave of these roles runs: counts it cannot reach are not compiled)
+            constexpr int MOST=STAGER ? Roles::spilled_tiles(0) : (SPILLED > 0 ? CT : (16+TILE_WAVES-1)/TILE_WAVES);
+            for (int done=0; done < tiles; done+=CT)
+              {
+                const int left=tiles-done;
+                if ((MOST >= CT) && (left >= CT))
+                  column_tiles(std::integral_constant<int,CT>{},done);
+                else if ((MOST >= 2) && (left == 2))
+                  column_tiles(std::integral_constant<int,2>{},done);
+                else
+                  column_tiles(std::integral_constant<int,1>{},done);
+              }
+          }
       MH_HTRACE_MARK(4);
       __syncthreads();                           // X: group g staged, the alpha of group g-1 published
       MH_HTRACE_MARK(5);
@@ -644,12 +726,12 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       {
         // the weights of this lane's four pixels of group g-1, read first: the chains below hide the LDS latency
         // (at the head of the epilogue's dependent chain it cost 0.04 ms per frame)
-        floatx4 weight={1.0f,1.0f,1.0f,1.0f};
+        // (a row wave of an alpha-weighted frame only: plain row waves multiply with `back`, other waves with nothing)
+        floatx4 weight;
+        if constexpr (BLEND && ROW)
+          weight=*reinterpret_cast<const floatx4 *>(alpha_weight+weight_slot(ot));
         if constexpr (BLEND)
-          if (row_wave)
-            weight=*reinterpret_cast<const floatx4 *>(alpha_weight+weight_slot(ot));
-        if constexpr (BLEND)
-          if (alpha_wave)
+          if constexpr (ALPHA)
             {
               // group g's byte-plane operands, for the chain of the next interval A (the planes are rewritten there)
               plane_low=*reinterpret_cast<const intx4 *>(alpha_plane+alpha_entry);
@@ -666,7 +748,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
         // of group g-1: the column pass's samples, UNROUNDED:
         //   alpha-weighted: A*R_c*2^-17 = S_c*weight (the alpha waves' weight, interval A)
         //   plain:          level/2 = S/scale
-        if (row_wave)
+        if constexpr (ROW)
           {
             floatx4 acc={0.0f,0.0f,0.0f,0.0f};
 #pragma unroll
@@ -679,7 +761,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
                 acc=__builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi,toeplitz_lo(c),acc,0,0,0);
               }
             float v[4];
-            if (BLEND)
+            if constexpr (BLEND)
               {
 #pragma unroll
                 for (int r=0; r < 4; r++)
@@ -703,14 +785,31 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc));
             sums_row=acc;
           }
-        // the store of the column pass's rows
-        store_row(cb,opaque_tid & 63);
+        // the store of the column pass's rows: wave = row of block cb
+        if (STEADY || ((cb >= 0) && (cb < nblocks)))
+          {
+            const int column=opaque_tid & 63;
+            const uint2 result=out_tile[wave*G::OUT_STRIDE+column];
+            const int x=x0+column,y=out_begin+G::GROUP*cb+wave;
+            if ((x < W) && (STEADY || (y < H)))
+              store_pixel16(args.dst+pixel_index(y,W,x)*PX,result);
+          }
       }
       MH_HTRACE_MARK(7);
       __syncthreads();                           // Y: ring group g-1 complete, out_tile read, staging reads done
       MH_HTRACE_MARK(8);
       ring_group=ring_group+1 == G::NR ? 0 : ring_group+1;
-    }
+    };
+    // fill and drain in the one tested body, the steady state between them in its own
+    for (int g=0; g < walk_end; g++)
+      {
+        if (g == steady_begin)
+          for (; g < steady_end; g++)
+            iteration(std::true_type{},g);
+        iteration(std::false_type{},g);
+      }
+  };
+  dispatch_roles<Roles,0>(wave,walk);
   MH_HITEM_STAMP(1);
   if ((args.recomputed != nullptr) && (recomputed != 0u) && (lane == 0))     // a wave-uniform count
     atomicAdd(args.recomputed,(unsigned long long) recomputed);
