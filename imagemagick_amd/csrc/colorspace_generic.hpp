@@ -3,8 +3,8 @@
 // and ConvertGenericToRGB (:122-305) for CMY, HCL, HCLp, HSB, HSI, HSL, HSV, HWB, LCHab (LCH),
 // LCHuv, Luv, LMS, CAT02LMS, xyY, YCbCr, YPbPr, YDbDr, YIQ, YUV, Jzazbz, OkLab, OkLCH, Adobe98,
 // DisplayP3 and ProPhoto, and ModulateImage's colour models built on them
-// (MagickCore/enhance.c:3462-3632).  Included by pointwise.hip after its gamma / XYZ / Lab / HSB
-// / HSL helpers.
+// (MagickCore/enhance.c:3462-3632).  The kernels of colorspace.hip's generic step and of
+// launch_modulate_generic; the gamma / XYZ / Lab / HSB / HSL helpers come from colour_math.hpp.
 //
 // One kernel with a wave-uniform switch on the colourspace: these are streams of fp64
 // arithmetic, the branch costs nothing next to a pow or an atan2.  Every expression keeps the
@@ -14,6 +14,13 @@
 // tie (Q16) and as at most one float ULP (float Quantum), which is what the tests allow.
 //
 // Formulas: MagickCore/colorspace-private.h — the line of each is cited at its restatement.
+#pragma once
+
+#include "device_common.hpp"
+#include "pixel_intensity.hpp"
+#include "colour_math.hpp"
+
+namespace mh {
 
 // ---------------------------------------------------------------- small helpers
 static __device__ __forceinline__ double cs_min3(double a,double b,double c)
@@ -815,3 +822,5 @@ void modulate_generic_kernel(Q *__restrict__ pixels,size_t npixels,int colorspac
       store_pixel<Q,C>(pixels+i*C,q);
     }
 }
+
+} // namespace mh

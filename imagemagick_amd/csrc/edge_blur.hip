@@ -34,13 +34,12 @@
 #include "mh_internal.hpp"
 #include "device_common.hpp"
 #include "layout_dispatch.hpp"
+#include "pixel_intensity.hpp"
 
 #include <algorithm>
 #include <vector>
 
 namespace mh {
-
-#include "pixel_intensity.inc.hpp"
 
 constexpr int kEdgeBlock=kWindowBlock;       // outputs per workgroup: kEdgeBlock x kEdgeBlock
 constexpr size_t kEdgeMaxLds=131072;         // bytes of the staged tile

@@ -1,9 +1,11 @@
 // Host-side helpers of the kernel launchers: the run-time pixel layout (Quantum type, channel
-// count, alpha blending) turned into template arguments, and the launch geometry of the operators
-// that stage a window in LDS for 16 x 16 outputs.
+// count, alpha blending) turned into template arguments, the launch geometry of the pointwise
+// streams and that of the operators that stage a window in LDS for 16 x 16 outputs.
 #pragma once
 
 #include "mh_internal.hpp"
+
+#include <type_traits>
 
 namespace mh {
 
@@ -16,21 +18,41 @@ struct Layout
   static constexpr bool BLEND=BLEND_;
 };
 
-// f(Layout<Q,C>{}) with Q = uint16_t (MH_QUANTUM_U16) or float and C = channels; a channel count
-// other than 1, 2 and 3 goes to C = 4.
+// f(c) with the compile-time value c.value = channels; a channel count other than 1, 2 and 3 goes
+// to 4.
+template<class F>
+static inline auto dispatch_channels(int channels,F &&f)
+{
+  switch (channels)
+  {
+    case 1: return f(std::integral_constant<int,1>{});
+    case 2: return f(std::integral_constant<int,2>{});
+    case 3: return f(std::integral_constant<int,3>{});
+    default: return f(std::integral_constant<int,4>{});
+  }
+}
+
+// f(Layout<Q,C>{}) with Q = uint16_t (MH_QUANTUM_U16) or float and C = channels, as above.
 template<class F>
 static inline auto dispatch_layout(MhQuantumKind quantum,int channels,F &&f)
 {
   const auto typed=[&](auto q)
   {
     using Q=decltype(q);
-    switch (channels)
-    {
-      case 1: return f(Layout<Q,1>{});
-      case 2: return f(Layout<Q,2>{});
-      case 3: return f(Layout<Q,3>{});
-      default: return f(Layout<Q,4>{});
-    }
+    return dispatch_channels(channels,[&](auto c) { return f(Layout<Q,c.value>{}); });
+  };
+  return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
+}
+
+// ... for the kernels that exist for R,G,B[,A] frames only: f receives Layout<Q,3> or Layout<Q,4>
+// and <Q,1>, <Q,2> are never instantiated.  The caller has rejected every other channel count.
+template<class F>
+static inline auto dispatch_colour_layout(MhQuantumKind quantum,int channels,F &&f)
+{
+  const auto typed=[&](auto q)
+  {
+    using Q=decltype(q);
+    return channels == 3 ? f(Layout<Q,3>{}) : f(Layout<Q,4>{});
   };
   return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
 }
@@ -50,6 +72,22 @@ static inline auto dispatch_layout_blend(MhQuantumKind quantum,int channels,bool
       }
     return f(L);
   });
+}
+
+// ------------------------------------------------------------ pointwise streams
+// Pointwise kernels keep kPointBatch pixels per lane in flight: with one 8-byte load per lane
+// the latency of the load -> (gather ->) compute -> store chain, not HBM, sets the rate
+// (measured 1.2 TB/s for the Lab kernel before batching).
+constexpr int kPointBatch=4;
+
+static unsigned stream_grid(size_t npixels)
+{
+  size_t blocks=(npixels+255)/256;
+  if (blocks > 8192)
+    blocks=8192;
+  if (blocks < 1)
+    blocks=1;
+  return (unsigned) blocks;
 }
 
 // ------------------------------------------------------------ 16 x 16 outputs per workgroup

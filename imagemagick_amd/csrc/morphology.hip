@@ -20,6 +20,7 @@
 #include "mh_internal.hpp"
 #include "device_common.hpp"
 #include "layout_dispatch.hpp"
+#include "pixel_intensity.hpp"
 #include <vector>
 
 #include <cmath>
@@ -27,8 +28,6 @@
 #include <algorithm>
 
 namespace mh {
-
-#include "pixel_intensity.inc.hpp"
 
 struct Cell
 {
@@ -61,7 +60,7 @@ constexpr int kTW=64;
 constexpr int kTH=16;
 constexpr int kRowsPerLane=4;
 
-// GetPixelIntensity for the *Intensity methods (pixel_intensity.inc.hpp).  The methods that need no gamma step
+// GetPixelIntensity for the *Intensity methods (pixel_intensity.hpp).  The methods that need no gamma step
 // are evaluated in line; a frame whose colourspace makes the method encode or decode its samples first (Rec709Luma
 // of linear RGB, the Luminance methods of sRGB: pixel.c:2418-2452) goes through the whole switch behind a call.
 template<typename Q,int C>

@@ -3,7 +3,7 @@
 // made of (exposed so a row-sharded image can all-reduce the histogram between
 // the phases — SURVEY §8e).
 //
-// The histogram and the LUT application are HIP kernels (pointwise.hip); the
+// The histogram and the LUT application are HIP kernels (histogram.hip); the
 // 65536-entry scans that turn a histogram into a LUT are restated here on the
 // host from MagickCore/enhance.c:1652-1706 (contrast stretch) and :2138-2169
 // (equalize), in the reference's arithmetic.
@@ -143,7 +143,7 @@ MhStatus apply_histogram_lut(const View &view,const MhImage *image,const unsigne
   if (!equalize && (view.channels <= 4) && (option("MAGICKHIP_NO_STRETCH_LEVELS") == nullptr))
     {
       // ContrastStretchImage: the levels of every channel, then the map evaluated per sample — no
-      // table to build and gather from (pointwise.hip)
+      // table to build and gather from (histogram.hip)
       uint32_t update=0;
       for (uint32_t c=0; c < image->number_channels; c++)
         if ((image->channel_traits[c] & MH_TRAIT_UPDATE) != 0)
@@ -167,7 +167,7 @@ MhStatus apply_histogram_lut(const View &view,const MhImage *image,const unsigne
   if (((mode != 0) || (view.channels == 1)) && (update != 0))
     shared_column=__builtin_ctz(update);
   // EqualizeImage on a float frame: the map evaluated per sample from the running counts in LDS
-  // instead of gathered from a 65536-float table (pointwise.hip)
+  // instead of gathered from a 65536-float table (histogram.hip)
   if (equalize && (view.quantum != MH_QUANTUM_U16) && (shared_column >= 0) && (view.channels <= 4) &&
       (view.columns*view.rows >= ((size_t) 1 << 20)) && (option("MAGICKHIP_NO_EQUALIZE_COUNTS") == nullptr))
     {
@@ -740,7 +740,7 @@ MH_API MhStatus MagickHipTransformImageColorspace(MhImage *image,MhColorspace co
 
 // TransformImageColorspace followed by ContrastStretchImage, as one call.  The results are those
 // of the two calls; what the pair can share is the pass over the pixels: FAST sRGB -> Lab on
-// RGBA Q16 converts and bins the intensity of what it stores in the same kernel (pointwise.hip,
+// RGBA Q16 converts and bins the intensity of what it stores in the same kernel (histogram.hip,
 // lab_histogram_fast_kernel).  MagickHipBatchImages uses it for adjacent operators of a chain.
 MH_API MhStatus MagickHipTransformColorspaceContrastStretchImage(MhImage *image,MhColorspace colorspace,
   double black_point,double white_point)
@@ -757,7 +757,7 @@ MH_API MhStatus MagickHipTransformColorspaceContrastStretchImage(MhImage *image,
       lab.colorspace=(uint32_t) MH_COLORSPACE_LAB;
       bool fused=false;
       {
-        // three launches: convert + bin, levels, map (pointwise.hip)
+        // three launches: convert + bin, levels, map (histogram.hip)
         uint32_t update=0;
         for (uint32_t c=0; c < image->number_channels; c++)
           if ((image->channel_traits[c] & MH_TRAIT_UPDATE) != 0)
@@ -929,7 +929,7 @@ MH_API MhStatus MagickHipFunctionImage(MhImage *image,MhFunction function,
 
 // ------------------------------------------------------------------ threshold.c
 // The frames the reference's IsGrayColorspace() holds for gray: fewer than three colour channels
-// are laid out that way whatever the descriptor's colourspace says (pixel_intensity.inc.hpp).
+// are laid out that way whatever the descriptor's colourspace says (pixel_intensity.hpp).
 static bool threshold_gray_frame(const MhImage *image)
 {
   const uint32_t colours=image->number_channels-(image->alpha_offset >= 0 ? 1u : 0u);

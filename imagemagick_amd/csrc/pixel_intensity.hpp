@@ -1,8 +1,15 @@
 // GetPixelIntensity (MagickCore/pixel.c:2356-2455) and the sRGB transfer functions it needs
 // (pixel.c:260-451), restated for the device.  Shared by the kernels that weigh pixels by their
-// intensity: Grayscale, Histogram and ContrastStretch (pointwise.hip), BilateralBlur and
-// SelectiveBlur (edge_blur.hip).  Textually included inside namespace mh, after
-// device_common.hpp.
+// intensity: Grayscale (pointwise.hip), Histogram and ContrastStretch (histogram.hip), pixel
+// export (pixel_io.hip), the *Intensity morphology methods (morphology.hip), the threshold
+// operators (threshold.hip), BilateralBlur and SelectiveBlur (edge_blur.hip), and by the
+// colourspace kernels (colorspace.hip, colour_math.hpp) for the transfer functions.
+#pragma once
+
+#include "mh_internal.hpp"
+#include "device_common.hpp"
+
+namespace mh {
 
 // --------------------------------------------------------------- sRGB gamma
 // x^2.4 via frexp + 9-term Chebyshev + power-of-two table, pixel.c:260-316
@@ -222,3 +229,5 @@ static __device__ __forceinline__ double pixel_intensity_of(const Q (&q)[C],cons
   else
     return pixel_intensity_call<Q,C>(q,ip);
 }
+
+} // namespace mh

@@ -8,9 +8,16 @@
 // "BGRA", ...) are the same arithmetic unrolled, except that export writes 0 for the pad of
 // "RGBP"/"BGRP" and leaves a pad untouched otherwise.  Conversions: quantum-private.h:435-535
 // (QuantumDepth 16, plain and HDRI), quantum.h:113-124 (ScaleQuantumToChar), quantum.h:86-97
-// (ClampToQuantum).
-// (Textually included at the end of pointwise.hip, inside namespace mh: it uses that file's
-// GetPixelIntensity restatement.)
+// (ClampToQuantum).  Export of an 'I' component uses the GetPixelIntensity restatement of
+// pixel_intensity.hpp.
+#include "mh_internal.hpp"
+#include "device_common.hpp"
+#include "pixel_intensity.hpp"
+
+#include <cstring>
+#include <strings.h>
+
+namespace mh {
 
 enum { kMaxComponents=8 };
 // what a component of the caller's buffer is
@@ -294,3 +301,4 @@ MhStatus launch_pixel_io(bool import,const View &img,const MhImage *desc,int x,i
   return launch_io_typed<float>(import,type,a,img.stream);
 }
 
+} // namespace mh

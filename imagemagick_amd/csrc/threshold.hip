@@ -33,12 +33,11 @@
 #include "mh_internal.hpp"
 #include "device_common.hpp"
 #include "layout_dispatch.hpp"
+#include "pixel_intensity.hpp"
 
 #include <algorithm>
 
 namespace mh {
-
-#include "pixel_intensity.inc.hpp"
 
 constexpr int kThresholdThreads=256;
 constexpr unsigned kThresholdMaxBlocks=1u << 20;

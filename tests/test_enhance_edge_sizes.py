@@ -1,6 +1,6 @@
 """Keeps the big-frame and block-boundary cases of tests/test_gpu_enhance_edges.py honest without a GPU: their sizes
 follow constants of the kernels' sources (stream_grid's block cap, the 256-thread block, kPointBatch), read here from
-pointwise.hip and morphology.hip the way the *_kernel_resources modules read ISA facts.  Whoever changes one of them
+layout_dispatch.hpp, pointwise.hip and morphology.hip the way the *_kernel_resources modules read ISA facts.  Whoever changes one of them
 gets a failure here instead of a GPU test that quietly stops covering the second trip of a grid-stride loop.  Also
 draws the first cases of the stress families 16 to 18 (no GPU needed: the decline conditions depend on shape and
 radius only) and checks the share of declined cases against the quarter the driver allows."""
@@ -39,14 +39,14 @@ def kernel_launch_bounds(text, kernel):
 
 
 def pointwise_constants():
-    text = source("pointwise.hip")
-    grid = function_body(text, "static unsigned stream_grid(size_t npixels)")
+    geometry = source("layout_dispatch.hpp")
+    grid = function_body(geometry, "static unsigned stream_grid(size_t npixels)")
     block = re.search(r"blocks=\(npixels\+(\d+)\)/(\d+);", grid)
     cap = re.search(r"if \(blocks > (\d+)\)\s*blocks=(\d+);", grid)
-    batch = re.search(r"constexpr int kPointBatch=(\d+);", text)
+    batch = re.search(r"constexpr int kPointBatch=(\d+);", geometry)
     assert block and cap and batch
     assert int(block.group(1)) + 1 == int(block.group(2)) and cap.group(1) == cap.group(2)
-    return int(cap.group(1)), int(block.group(2)), int(batch.group(1)), text
+    return int(cap.group(1)), int(block.group(2)), int(batch.group(1)), source("pointwise.hip")
 
 
 def test_big_frames_sit_just_above_one_trip_of_the_grid_stride_loops():

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 Q16, HDRI = np.uint16, np.float32
 
-# The sizes of the grid-stride cases follow three constants of pointwise.hip (stream_grid's block cap, the block
+# The sizes of the grid-stride cases follow three constants of layout_dispatch.hpp and pointwise.hip (stream_grid's block cap, the block
 # width and kPointBatch); tests/test_enhance_edge_sizes.py reads them from the source and fails when these frames
 # stop being "just above" one trip of the loops.
 STREAM_CAP_BLOCKS, BLOCK_WIDTH, POINT_BATCH = 8192, 256, 4

@@ -1,6 +1,6 @@
 """ContrastStretchImage / EqualizeImage (MagickCore/enhance.c:1544-1818, :2040-2280) on the device, through the C ABI,
 against the compiled reference: the level-scan edges, the binning edges, the channel masks and the frame sizes at which
-the launchers of pointwise.hip change kernels.  Every comparison is bit for bit (float results as bit patterns), in
+the launchers of histogram.hip change kernels.  Every comparison is bit for bit (float results as bit patterns), in
 EXACT and in FAST: nothing on these paths reads the precision.  The one exception is the fused FAST sRGB -> Lab +
 stretch (part I), whose Lab frame is within one level of the reference and whose stretch is exact on that frame.
 

@@ -6,7 +6,7 @@ than their kernel, and the two methods the library declines.
 
 Found with these tests, fixed in morphology.hip: Erode/DilateIntensity (and Open/CloseIntensity) of a linear-RGB
 frame were declined ("intensity method needs a gamma transform") although the device restatement of
-GetPixelIntensity the other operators use (pixel_intensity.inc.hpp) is bit-exact; the generic kernel now calls it
+GetPixelIntensity the other operators use (pixel_intensity.hpp) is bit-exact; the generic kernel now calls it
 where the method encodes or decodes the samples first."""
 import ctypes
 

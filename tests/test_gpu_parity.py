@@ -1976,7 +1976,7 @@ def test_colorspace(im, refmod, dtype, src, dst, channels):
 @pytest.mark.parametrize("black,white", [(0.02, 0.01), (0.0, 0.0), (0.7, 0.6), (1.5, 0.0), (0.0, 1.5)])
 def test_lab_contrast_stretch_three_launches(im, frame, black, white, options):
     """FAST sRGB->Lab + ContrastStretch in one call on RGBA Q16 takes three launches (convert + bin,
-    stretch_levels_kernel, stretch_apply_kernel: pointwise.hip); the levels and the map are those
+    stretch_levels_kernel, stretch_apply_kernel: histogram.hip); the levels and the map are those
     of the general route (slab reduction, three LUT kernels, LUT apply), bit for bit — on frames
     whose shares overflow the packed counters' capacity into the extra-pixel lists, on a constant
     frame (one bin holds everything), with thresholds no bin reaches and thresholds every bin

@@ -1,6 +1,6 @@
 """Keeps the sizes of tests/test_gpu_histogram_edges.py tied to the constants of the kernels they are meant to straddle,
 without a GPU: the `1 << 20` switches of the launchers, kPackedCapacity, kHistHalf and the 16-bin group of
-equalize_cdf_apply_kernel, read from pointwise.hip and operators_enhance.cpp the way tests/test_enhance_edge_sizes.py
+equalize_cdf_apply_kernel, read from histogram.hip and operators_enhance.cpp the way tests/test_enhance_edge_sizes.py
 reads its constants.  Whoever moves one of them gets a failure here instead of a GPU test that quietly stops covering
 both sides."""
 import re
@@ -12,11 +12,13 @@ SWITCH = "((size_t) 1 << 20)"
 
 
 def test_large_shapes_straddle_the_megapixel_switches():
-    text = source("pointwise.hip")
+    text = source("histogram.hip")
     assert "(mode != 0) && (n >= %s)" % SWITCH in function_body(text, "static MhStatus histogram_typed(")
     assert "(img.columns*img.rows >= %s)" % SWITCH in function_body(text, "MhStatus launch_apply_lut(")
+    # the two fused Lab launchers share one gate
+    assert "(n < %s)" % SWITCH in function_body(text, "static size_t lab_histogram_fast_blocks(")
     for launcher in ("MhStatus launch_lab_fast_with_histogram(", "MhStatus launch_lab_fast_contrast_stretch("):
-        assert "(n < %s)" % SWITCH in function_body(text, launcher)
+        assert "lab_histogram_fast_blocks(img)" in function_body(text, launcher)
     enhance = function_body(source("operators_enhance.cpp"), "MhStatus apply_histogram_lut(")
     assert "(view.columns*view.rows >= %s)" % SWITCH in enhance
     assert edges.THRESHOLD == 1 << 20
@@ -30,7 +32,7 @@ def test_large_shapes_straddle_the_megapixel_switches():
 
 
 def test_packed_counter_cases_follow_the_capacity():
-    text = source("pointwise.hip")
+    text = source("histogram.hip")
     capacity = int(re.search(r"constexpr unsigned kPackedCapacity=(\d+)u;", text).group(1))
     assert capacity == edges.PACKED_CAPACITY and capacity < 65536 and capacity % 2 == 0
     blocks = function_body(text, "static size_t packed_histogram_blocks(int device,size_t n)")
@@ -52,7 +54,7 @@ def test_packed_counter_cases_follow_the_capacity():
 
 
 def test_planted_samples_sit_on_both_sides_of_the_half_range():
-    text = source("pointwise.hip")
+    text = source("histogram.hip")
     half = int(re.search(r"constexpr int kHistHalf=(\d+);", text).group(1))
     assert half == edges.HIST_HALF == 32768
     assert "const unsigned base=(unsigned) half*kHistHalf;" in function_body(text, "void histogram_lds_kernel(")
@@ -60,7 +62,7 @@ def test_planted_samples_sit_on_both_sides_of_the_half_range():
 
 
 def test_group_counts_straddle_the_equalize_fallback():
-    kernel = function_body(source("pointwise.hip"), "void equalize_cdf_apply_kernel(")
+    kernel = function_body(source("histogram.hip"), "void equalize_cdf_apply_kernel(")
     assert "first=cdf[j & ~15];" in kernel and "base[j >> 4]" in kernel and "if (d > 65535u)" in kernel
     assert edges.GROUP == 16 and edges.GROUP_FIRST_BIN % edges.GROUP == 0
     assert edges.GROUP_COUNTS == (65535, 65536)
