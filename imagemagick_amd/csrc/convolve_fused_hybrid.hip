@@ -207,6 +207,14 @@ static __device__ __forceinline__ void dispatch_roles(int wave,const Walk &walk)
 #define MH_HITEM_STAMP(slot) do { } while (0)
 #endif
 
+// A read at an LDS byte ADDRESS (not an offset into the dynamic array): a loop-invariant address kept in a register
+// is used as it stands, where array + offset leaves the sum to be formed again in every iteration.
+template<class T>
+static __device__ __forceinline__ T lds_read_at(int address)
+{
+  return *reinterpret_cast<const __attribute__((address_space(3))) T *>((size_t) address);
+}
+
 template<int NC,int MODE>
 __global__ __launch_bounds__(1024)
 void blur_fused_hybrid_kernel(BlurExactArgs args)
@@ -237,14 +245,15 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   typedef HybridGeometry<NC,BLEND> G;
   typedef Fused16Geometry<NC> F;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  _Float16 *ring_hi=reinterpret_cast<_Float16 *>(smem_raw);
-  _Float16 *ring_lo=ring_hi+F::RING_PLANE;
+  // (the ring's hi plane at byte 0, its lo plane behind it: addressed in bytes, see GROUP_BYTES)
   _Float16 *stage_hi=reinterpret_cast<_Float16 *>(smem_raw+G::ring_bytes);
   _Float16 *stage_lo=stage_hi+G::STAGE_PLANE;
   unsigned char *alpha_plane=smem_raw+G::ring_bytes+G::stage_bytes;      // [2][GROUP][ASTRIDE]
   float *alpha_weight=reinterpret_cast<float *>(alpha_plane+G::alpha_bytes); // [COLS][GROUP]
   uint2 *out_tile=reinterpret_cast<uint2 *>(alpha_plane+G::alpha_bytes+G::sum_bytes);
   unsigned char *digit_table=alpha_plane+G::alpha_bytes+G::sum_bytes+G::out_bytes;   // [4][kExactDigits][DLP]
+  const int lds_base=(int) (size_t) (__attribute__((address_space(3))) unsigned char *) smem_raw;
+  typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
   const int tid=(int) threadIdx.x,lane=tid & 63;
   const int wave=__builtin_amdgcn_readfirstlane(tid >> 6);
   const int n=lane & 15,kq=lane >> 4;
@@ -367,12 +376,17 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   }
 
   // ---- staging: thread -> (row, 4 consecutive columns) of the 16 x XS source window
-  // (the walk recomputes a stager's row and column group from its thread index in every iteration
-  // — a handful of vector instructions — instead of keeping them, the addresses derived from
-  // them and the other loop-invariant indices in registers: the kernel sits at the 128 registers
-  // of a wave, and what the compiler spills it reloads from scratch INSIDE the walk, each reload
-  // behind an s_waitcnt vmcnt(0) that also waits for the prefetched pixels: 9 such reloads cost
-  // 0.25 ms per 8192^2 frame.)  Both lambdas are called from the staging waves' walks only.
+  // A stager's row and column group do not change over the walk, and neither does anything formed from them: the
+  // walk keeps the LDS addresses it stages to and the byte offsets of its pixels within a group of 16 source rows
+  // (StagerLane, formed once in front of the walk) and reaches the rows through a workgroup-uniform row base that is
+  // advanced on the scalar side.  The steady state, whose rows all lie inside the image, forms no address on the vector
+  // pipe at all (fetch_steady); fill, drain and the iterations whose rows are clamped to the image (fetch) form the
+  // clamped rows per lane, from a thread index the optimiser cannot see through: what it hoisted out of those few
+  // iterations would hold registers through the whole walk.  (The single-loop kernel recomputed everything in every
+  // iteration for that reason: at 126-128 registers the compiler spilled what it kept and reloaded it inside the walk,
+  // each reload behind an s_waitcnt vmcnt(0) that also waits for the prefetched pixels.  With one walk per set of roles
+  // the kernel has the registers: tests/test_kernel_resources.py holds it to 128 and no scratch.)
+  // All of it is called from the staging waves' walks only.
   // An EDGE item: its staged window hangs over the image's left or right edge (the first and the last strip, every
   // segment of them), so some of its column groups are clamped.  Decided per ITEM — workgroup-uniform, a scalar
   // branch — and not per lane: a stager is thread tid/GROUPS_PER_ROW's row, so every staging wave of an edge item
@@ -427,14 +441,75 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
           }
       }
   };
+  // What a stager keeps over the walk: where it stages to (LDS byte addresses: its four columns in the first f16
+  // plane, in the low alpha plane) and where its pixels lie in a group of 16 source rows — bytes from the first pixel
+  // of the group's first row: (srow*W + column)*PX*2 < 16 * 2^24 * 8 = 2^31 under the launcher's limits.  An interior
+  // item's four columns are one run (source[0]); an edge item's are clamped one by one, once.
+  struct StagerLane { int stage,line; unsigned source[4]; };
+  auto stager_lane=[&](int srow,int sxg) -> StagerLane
+  {
+    StagerLane at;
+    at.stage=G::ring_bytes+2*(srow*F::SR+4*sxg);
+    at.line=G::ring_bytes+G::stage_bytes+srow*G::ASTRIDE+4*sxg;
+    asm volatile("" : "+v"(at.stage),"+v"(at.line));
+#pragma unroll
+    for (int i=0; i < 4; i++)
+      {
+        int x=xin0+4*sxg+i;
+        x=x < 0 ? 0 : (x > W-1 ? W-1 : x);
+        at.source[i]=(unsigned) (srow*W+x)*(unsigned) (PX*2);
+      }
+    // (formed here and nowhere else: opaque, so that the walk cannot form them again in every iteration)
+    asm volatile("" : "+v"(at.source[0]),"+v"(at.source[1]),"+v"(at.source[2]),"+v"(at.source[3]));
+    return at;
+  };
+  // the steady state's fetch: `rows` = the first pixel of the group's first row, a workgroup-uniform address in scalar
+  // registers; every one of the 16 rows lies inside the image.  The loads take the scalar base and the lane's 32-bit
+  // offset as they are.
+  // (The offsets pass through an empty asm where they are used: the widening of a 32-bit offset has to stand beside
+  // its load for the load to take base and offset apart, and the optimiser moves what is loop-invariant out of the
+  // walk.)
+  auto fetch_steady=[&](auto edge,const unsigned char *rows,StagerLane &at)
+  {
+    if constexpr (!decltype(edge)::value)
+      {
+        asm volatile("" : "+v"(at.source[0]));
+        if constexpr (MODE == MFMA_PLAIN3)
+          {
+            const LooseDword *words=reinterpret_cast<const LooseDword *>(rows+at.source[0]);
+            const uint2 a=make_uint2(words[0],words[1]),b=make_uint2(words[2],words[3]),c=make_uint2(words[4],words[5]);
+            raw[0]=make_uint2(a.x,a.y & 0xffffu);
+            raw[1]=make_uint2((a.y >> 16) | (b.x << 16),b.x >> 16);
+            raw[2]=make_uint2(b.y,c.x & 0xffffu);
+            raw[3]=make_uint2((c.x >> 16) | (c.y << 16),c.y >> 16);
+          }
+        else
+          {
+            typedef unsigned LooseQuad __attribute__((ext_vector_type(4),aligned(8)));
+            const LooseQuad *quads=reinterpret_cast<const LooseQuad *>(rows+at.source[0]);
+            const LooseQuad a=quads[0],b=quads[1];
+            raw[0]=make_uint2(a[0],a[1]);
+            raw[1]=make_uint2(a[2],a[3]);
+            raw[2]=make_uint2(b[0],b[1]);
+            raw[3]=make_uint2(b[2],b[3]);
+          }
+      }
+    else
+      {
+        asm volatile("" : "+v"(at.source[0]),"+v"(at.source[1]),"+v"(at.source[2]),"+v"(at.source[3]));
+#pragma unroll
+        for (int i=0; i < 4; i++)
+          raw[i]=load_pixel16(reinterpret_cast<const uint16_t *>(rows+at.source[i]));
+      }
+  };
   // raw Quantum pixels -> the f16 operand planes (alpha*p*2^-17 per colour channel, or level/2 of
   // a plain channel: hi/lo split) and, alpha-weighted frames, the alpha levels as two byte planes
-  auto stage_group=[&](int srow,int sxg)
+  auto stage_group=[&](const StagerLane &at)
   {
     f32x2 v[4][2];
     quantum_to_samples<SAMPLES>(raw,v);
     // (one address + immediate offsets)
-    unsigned char *to=smem_raw+G::ring_bytes+2*(srow*F::SR+4*sxg);
+    unsigned char *to=smem_raw+at.stage;
     // (RGB frames: the fourth plane stays as it is — its row tiles are not run, what the column pass makes of it
     // stays in the entries of the channel that is not stored)
     constexpr int STAGED=MODE == MFMA_PLAIN3 ? 3 : G::STAGE_CHANNELS;
@@ -451,7 +526,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       {
         // bytes 2,3 of the second word of each pixel = the alpha level, paired over the four positions
         const unsigned hy01=__builtin_amdgcn_perm(raw[1].y,raw[0].y,0x07030602u),hy23=__builtin_amdgcn_perm(raw[3].y,raw[2].y,0x07030602u);
-        unsigned char *line=smem_raw+G::ring_bytes+G::stage_bytes+srow*G::ASTRIDE+4*sxg;
+        unsigned char *line=smem_raw+at.line;
         *reinterpret_cast<unsigned *>(line)=__builtin_amdgcn_perm(hy23,hy01,0x05040100u) ^ 0x80808080u;
         *reinterpret_cast<unsigned *>(line+G::GROUP*G::ASTRIDE)=__builtin_amdgcn_perm(hy23,hy01,0x07060302u) ^ 0x80808080u;
       }
@@ -497,12 +572,37 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       ctiles=Roles::spilled_tiles(wave);
       ctile0=CT*TILE_WAVES+wave*(SPILLED/4)+(wave < SPILLED % 4 ? wave : SPILLED % 4);
     }
-  constexpr int GROUP_STRIDE=2*F::OB;          // f16 ring: halves per 16-row group
-  const int col_entry16=(n & 3)*F::CHC+(4*ctile0+(n >> 2))*8+(kq & 1)*F::OB;
+  // The ring, addressed in BYTES of its hi plane (the lo plane lies RING_LO bytes on, an immediate offset): a lane's
+  // entry is loop-invariant and kept, the group's slot is a workgroup-uniform scalar — an access costs one add.
+  constexpr int GROUP_BYTES=(int) (2*F::OB*sizeof(_Float16));      // a 16-row group
+  constexpr int RING_LO=(int) (F::RING_PLANE*sizeof(_Float16));
+  static_assert(RING_LO+GROUP_BYTES < 65536,"the lo plane is an immediate offset away");
+  // column pass: lane (n, kq) reads 8 rows of channel n & 3, column 4*tile + (n >> 2): octet kq & 1 of ring group
+  // 2*c + (kq >> 1) of chunk c.  The two groups' slots are scalars; upper_half (all ones where kq >> 1) picks.
+  int col_entry=(int) (((n & 3)*F::CHC+(4*ctile0+(n >> 2))*8+(kq & 1)*F::OB)*sizeof(_Float16));
+  int upper_half=-(kq >> 1);
   // the row epilogue's ring store: lane (n, kq) holds rows 4*kq..+3 of channel rc, column 16*ot+n
-  const int ring_entry16=rc*F::CHC+(kq >> 1)*F::OB+(16*ot+n)*8+4*(kq & 1);
+  int ring_entry=(int) ((rc*F::CHC+(kq >> 1)*F::OB+(16*ot+n)*8+4*(kq & 1))*sizeof(_Float16));
   // ... the alpha wave's: rows 4*kq..+3 of the alpha channel, column 16*t+n
-  const int ring_alpha16=3*F::CHC+(kq >> 1)*F::OB+(16*alpha_tile+n)*8+4*(kq & 1);
+  int ring_alpha=(int) ((3*F::CHC+(kq >> 1)*F::OB+(16*alpha_tile+n)*8+4*(kq & 1))*sizeof(_Float16));
+  // the store of a finished row: wave = row of the block, lane = column of the strip.  Where the lane finds its pixel
+  // in out_tile (an LDS address: lds_read_at) and in a row of the destination (bytes from the strip's first column)
+  int out_entry=lds_base+G::ring_bytes+G::stage_bytes+G::alpha_bytes+G::sum_bytes+(wave*G::OUT_STRIDE+lane)*(int) sizeof(uint2);
+  unsigned dst_entry=(unsigned) (lane*PX*2);
+  // (opaque: formed once, here)
+  asm volatile("" : "+v"(col_entry),"+v"(upper_half),"+v"(ring_entry),"+v"(ring_alpha),"+v"(out_entry),"+v"(dst_entry));
+  // a strip whose 64 columns all lie inside the image stores its rows without a lane test; the last strip of other
+  // widths under a loop-invariant lane mask (a scalar pair)
+  const bool full_strip=x0+G::COLS <= W;
+  unsigned long long live_columns=__builtin_amdgcn_ballot_w64(x0+lane < W);
+  asm volatile("" : "+s"(live_columns));
+  // The steady state is compiled once per kind of item, so that no iteration tests the kind: an interior item (group
+  // loads, whole rows), an edge item (clamped columns) whose strip is full, and the rest — a strip of fewer than 64
+  // columns is the image's last, its window hangs over the right edge; the clamped loads are right for any item.
+  // (One steady body that branches on the item's scalars: the two stores, alike but for the mask, are merged behind
+  // the branch into one store under a mask, and a load in another block than its offset takes a 64-bit address.)
+  enum : int { WALK_TESTED=0,STEADY_INTERIOR=1,STEADY_EDGE=2,STEADY_RAGGED=3 };
+  const int steady_kind=!full_strip ? STEADY_RAGGED : (edge_item ? STEADY_EDGE : STEADY_INTERIOR);
   // the weights of rows 4*kq..+3 of column 16*t+n: 16 bytes, the four row quads of a column swizzled with the
   // column so that the 16 lanes of a b128 group (16 columns) fall into 16 different bank slots
   auto weight_slot=[&](int tile) { return (16*tile+n)*G::GROUP+4*(kq ^ ((n >> 2) & 3)); };
@@ -522,18 +622,34 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // youngest waves of their SIMDs, the alpha waves issued their 18 matrix instructions behind the 27 of the row
   // waves, and the interval lasted until they were through.)
   //
-  // The walk is compiled once per set of roles (HybridRoles) and, in each, twice: the iterations
+  // The walk is compiled once per set of roles (HybridRoles) and, in each, as a tested body and a steady state (the
+  // latter once per kind of item, steady_kind: which one runs is decided once, in front of it): the iterations
   //   fill    g <= NG                     nothing to run the column pass on yet
   //   steady  NG+1 <= g <= ngroups-2      (none when the item has fewer than four blocks)
   //   drain   ngroups-1 <= g <= ngroups+1 nothing left to stage, then to fetch
   // differ only in which of g < ngroups, g+1 < ngroups, 0 <= cb < nblocks and g >= 1 hold: all of them in the steady
   // state, whose body (STEADY) tests none and stores whole rows (a block before the item's last lies inside the
-  // image).  Fill and drain share the body that tests them.  The bounds below are the same scalars for every role,
-  // and both barriers of an iteration stand in the one body every role is compiled from, outside the roles' code: a
-  // wave passes 2*walk_end barriers whatever it is.
-  const int steady_begin=G::NG+1;
-  const int steady_end=ngroups-1 > steady_begin ? ngroups-1 : steady_begin;
+  // image).  Fill and drain share the body that tests them.
+  // The steady state also clamps no source row: the rows it fetches, in0+16*(g+1) .. +15 of group g+1, lie inside the
+  // image.  Above: 16*(g+1) >= 32*NC+32 in the steady state and in0 >= -shift > -(32*NC-15), the longest kernel of NC
+  // chunks — the bound is formed all the same.  Below: the image's last segment ends its steady state where its fetch
+  // would first reach row H, a few iterations early; they run in the tested body, which clamps.
+  // The bounds below are the same scalars for every role, and both barriers of an iteration stand in the one body
+  // every role is compiled from, outside the roles' code: a wave passes 2*walk_end barriers whatever it is.
+  const int first_inside=in0 < 0 ? (15-in0)/16-1 : 0;          // the first g with in0+16*(g+1) >= 0
+  const int end_inside=(H-in0)/16-1;                           // the first g with in0+16*(g+1)+15 > H-1 (H > in0)
+  const int steady_begin=G::NG+1 > first_inside ? G::NG+1 : first_inside;
+  const int steady_last=ngroups-1 < end_inside ? ngroups-1 : end_inside;
+  const int steady_end=steady_last > steady_begin ? steady_last : steady_begin;
   const int walk_end=ngroups+2;                  // > steady_end: the drain is never empty
+  // the steady state's row bases, workgroup-uniform: the first source row of the group its first iteration fetches
+  // (steady_begin+1) and the destination row its first iteration stores in this wave (row `wave` of block
+  // steady_begin-NG-1, from the strip's first column); both move on by 16 rows an iteration
+  const size_t group_bytes=(size_t) G::GROUP*(size_t) W*(size_t) (PX*2);
+  // (as byte distances from the frames' first pixels: see the walk)
+  const size_t steady_source=(size_t) (in0+G::GROUP*(steady_begin+1))*(size_t) W*(size_t) (PX*2);
+  const size_t steady_destination=
+    ((size_t) (out_begin+G::GROUP*(steady_begin-G::NG-1)+wave)*(size_t) W+(size_t) x0)*(size_t) (PX*2);
   auto walk=[&](auto roles) __attribute__((always_inline))
   {
     constexpr unsigned ROLES=decltype(roles)::value;
@@ -545,34 +661,61 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
     floatx4 sums_row={0.0f,0.0f,0.0f,0.0f};      // ROW
     intx4 plane_low={0,0,0,0},plane_high={0,0,0,0};   // ALPHA
     long plane_low2=0,plane_high2=0;
+    // the steady state's row bases (scalars)
+    size_t source_rows=steady_source,destination_rows=steady_destination;
+    StagerLane staged={0,0,{0u,0u,0u,0u}};
     if constexpr (STAGER)
-      fetch(0,tid/G::GROUPS_PER_ROW,tid % G::GROUPS_PER_ROW);
+      {
+        staged=stager_lane(tid/G::GROUPS_PER_ROW,tid % G::GROUPS_PER_ROW);
+        fetch(0,tid/G::GROUPS_PER_ROW,tid % G::GROUPS_PER_ROW);
+      }
+    // an alpha wave's loop-invariant operands: where it reads its byte planes (the low plane's LDS address; the
+    // high plane an immediate offset on), the second chunk's (kernels of more than 49 taps), and which of its lanes'
+    // columns lie inside the image (a scalar pair)
+    int plane_entry=lds_base+G::ring_bytes+G::stage_bytes+alpha_entry,plane_entry2=plane_entry+64-8*kq;
+    unsigned long long live_alpha=0ull;
+    if constexpr (ALPHA)
+      {
+        live_alpha=__builtin_amdgcn_ballot_w64(x0+16*alpha_tile+n < W);
+        asm volatile("" : "+v"(plane_entry),"+v"(plane_entry2),"+s"(live_alpha));
+      }
     // (s_setprio 3 for the alpha waves — the youngest waves of their SIMDs, with the longest chain of interval A —
     // only changes who waits: 0.528 against 0.522 ms, profiles/r6_notes/hybrid_blur_steps.txt)
-    auto iteration=[&](auto steady,const int g) __attribute__((always_inline))
+    auto iteration=[&](auto kind,const int g) __attribute__((always_inline))
     {
-      constexpr bool STEADY=decltype(steady)::value;
+      constexpr int KIND=decltype(kind)::value;
+      constexpr bool STEADY=KIND != WALK_TESTED,EDGE=KIND != STEADY_INTERIOR,FULL=KIND != STEADY_RAGGED;
       const int cb=g-G::NG-1;                    // the column pass's block of this iteration
       const int first=ring_group;                // ring slot of group cb: (g-NG-1) mod NR = g mod NR
       const int previous=ring_group == 0 ? G::NR-1 : ring_group-1;   // ring slot of group g-1
-      // a stager's row and column group, not loop-invariant to the optimiser (see the staging lambdas); the other
-      // waves have neither
-      int opaque_tid=tid,srow=0,sxg=0;
-      if constexpr (STAGER)
-        {
-          asm volatile("" : "+v"(opaque_tid));
-          srow=opaque_tid/G::GROUPS_PER_ROW;
-          sxg=opaque_tid-srow*G::GROUPS_PER_ROW;
-        }
       MH_HTRACE_MARK(0);
       if (STEADY || (g < ngroups))
         {
           if constexpr (STAGER)
-            stage_group(srow,sxg);
+            stage_group(staged);
           MH_HTRACE_MARK(1);
           if constexpr (STAGER)
-            if (STEADY || (g+1 < ngroups))
-              fetch(g+1,srow,sxg);
+            {
+              if constexpr (STEADY)
+                {
+                  // (the distance opaque, in scalar registers: left to itself the optimiser adds the lane's offset to
+                  // the walk's first base once, as a 64-bit address in vector registers, and the scalar distance
+                  // walked so far to that in every iteration)
+                  asm volatile("" : "+s"(source_rows));
+                  fetch_steady(std::integral_constant<bool,EDGE>{},reinterpret_cast<const unsigned char *>(args.src)+
+                    source_rows,staged);
+                  source_rows+=group_bytes;
+                }
+              else if (g+1 < ngroups)
+                {
+                  // the tested body clamps its rows per lane: a stager's row and column group again, from a thread
+                  // index that is not loop-invariant to the optimiser (see the staging lambdas)
+                  int opaque_tid=tid;
+                  asm volatile("" : "+v"(opaque_tid));
+                  const int srow=opaque_tid/G::GROUPS_PER_ROW;
+                  fetch(g+1,srow,opaque_tid-srow*G::GROUPS_PER_ROW);
+                }
+            }
         }
       MH_HTRACE_MARK(2);
       // ======================================================================== interval A
@@ -613,7 +756,6 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             exact_sums(tiles,args.offset,sums_alpha);
             unsigned q[4];
             const bool doubtful=exact_levels<false>(sums_alpha,args,q);
-            const int x=x0+16*alpha_tile+n;
             {
               // the alpha levels of sample v of the windows of lane `from`'s four rows
               auto fetch_alpha=[&](int from,int v,unsigned (&level)[4])
@@ -632,7 +774,7 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
               // comparison, combined on the scalar side and opaque from there on.  The mask of the combined per-lane
               // flag — or a branch on that flag, which `ballot != 0` is turned back into — goes through a vector
               // register: a v_cndmask 0/1 and a v_cmp_ne in every iteration.)
-              unsigned long long todo=__builtin_amdgcn_ballot_w64(doubtful) & __builtin_amdgcn_ballot_w64(x < W);
+              unsigned long long todo=__builtin_amdgcn_ballot_w64(doubtful) & live_alpha;
               if (!STEADY && !((g >= 1) && (g-1 < ngroups)))
                 todo=0ull;
               asm volatile("" : "+s"(todo));
@@ -645,9 +787,9 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             uint2 hi,lo;
             split_f16_pair(f32x2{half_level[0],half_level[1]},hi.x,lo.x);
             split_f16_pair(f32x2{half_level[2],half_level[3]},hi.y,lo.y);
-            const int at=ring_alpha16+previous*GROUP_STRIDE;     // group g-1's slot
-            *reinterpret_cast<uint2 *>(ring_hi+at)=hi;
-            *reinterpret_cast<uint2 *>(ring_lo+at)=lo;
+            unsigned char *at=smem_raw+(ring_alpha+previous*GROUP_BYTES);     // group g-1's slot
+            *reinterpret_cast<uint2 *>(at)=hi;
+            *reinterpret_cast<uint2 *>(at+RING_LO)=lo;
             // ... and the weight every colour sum of the pixel is multiplied with: the column pass's sample is
             // A*R_c*2^-17 with A = the exact level, R_c = sum(k*alpha*p)/sum(k*alpha) = 2^17*S_c/(scale*D), D the
             // REAL alpha sum in levels.  An all-transparent window: D = 0 and A = 0 -> 0*inf = NaN, which the
@@ -664,13 +806,17 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       if constexpr (COLUMN)
         if (STEADY || ((cb >= 0) && (cb < nblocks)))
           {
+            // chunk c reads ring groups first+2*c and first+2*c+1 (mod NR): both slots on the scalar side, the lane's
+            // own by its loop-invariant mask — an and and an add a chunk
             int chunk_at[NC];
+            int slot=first*GROUP_BYTES;
+            auto next_slot=[](int s) { return s+GROUP_BYTES == G::NR*GROUP_BYTES ? 0 : s+GROUP_BYTES; };
 #pragma unroll
             for (int c=0; c < NC; c++)
               {
-                const unsigned wide=(unsigned) (first+2*c+(kq >> 1));
-                const unsigned group=wide < wide-(unsigned) G::NR ? wide : wide-(unsigned) G::NR;
-                chunk_at[c]=col_entry16+GROUP_STRIDE*(int) group;
+                const int upper=next_slot(slot);
+                chunk_at[c]=col_entry+slot+(upper_half & (upper-slot));
+                slot=next_slot(upper);
               }
             auto column_tiles=[&](auto count,int done)
             {
@@ -686,8 +832,9 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
 #pragma unroll
                   for (int i=0; i < N; i++)
                     {
-                      a_hi[i]=*reinterpret_cast<const half8 *>(ring_hi+chunk_at[c]+4*(done+i)*F::SC);
-                      a_lo[i]=*reinterpret_cast<const half8 *>(ring_lo+chunk_at[c]+4*(done+i)*F::SC);
+                      const unsigned char *at=smem_raw+chunk_at[c]+4*(done+i)*F::SC*(int) sizeof(_Float16);
+                      a_hi[i]=*reinterpret_cast<const half8 *>(at);
+                      a_lo[i]=*reinterpret_cast<const half8 *>(at+RING_LO);
                     }
 #pragma unroll
                   for (int i=0; i < N; i++)
@@ -734,13 +881,13 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
           if constexpr (ALPHA)
             {
               // group g's byte-plane operands, for the chain of the next interval A (the planes are rewritten there)
-              plane_low=*reinterpret_cast<const intx4 *>(alpha_plane+alpha_entry);
-              plane_high=*reinterpret_cast<const intx4 *>(alpha_plane+G::GROUP*G::ASTRIDE+alpha_entry);
+              plane_low=lds_read_at<intx4>(plane_entry);
+              plane_high=lds_read_at<intx4>(plane_entry+G::GROUP*G::ASTRIDE);
               if constexpr (G::NX == 2)
                 {
-                  const int at=alpha_entry+64-8*kq;          // columns 64+8*kq .. +7
-                  plane_low2=*reinterpret_cast<const long *>(alpha_plane+at);
-                  plane_high2=*reinterpret_cast<const long *>(alpha_plane+G::GROUP*G::ASTRIDE+at);
+                  // columns 64+8*kq .. +7
+                  plane_low2=lds_read_at<long>(plane_entry2);
+                  plane_high2=lds_read_at<long>(plane_entry2+G::GROUP*G::ASTRIDE);
                 }
             }
         MH_HTRACE_MARK(6);
@@ -777,21 +924,40 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             uint2 hi,lo;
             split_f16_pair(f32x2{v[0],v[1]},hi.x,lo.x);
             split_f16_pair(f32x2{v[2],v[3]},hi.y,lo.y);
-            const int at=ring_entry16+previous*GROUP_STRIDE;
-            *reinterpret_cast<uint2 *>(ring_hi+at)=hi;
-            *reinterpret_cast<uint2 *>(ring_lo+at)=lo;
+            unsigned char *at=smem_raw+(ring_entry+previous*GROUP_BYTES);
+            *reinterpret_cast<uint2 *>(at)=hi;
+            *reinterpret_cast<uint2 *>(at+RING_LO)=lo;
             // (the wait states between the chain and the first vector read of its tile, whatever the
             // block layout: hipcc pads them per basic block — see settle_tiles)
             asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc));
             sums_row=acc;
           }
         // the store of the column pass's rows: wave = row of block cb
-        if (STEADY || ((cb >= 0) && (cb < nblocks)))
+        // (steady state: the row lies inside the image; its address is the scalar row base and the lane's offset, the
+        // lane's pixel of out_tile a loop-invariant LDS address)
+        if constexpr (STEADY)
           {
-            const int column=opaque_tid & 63;
-            const uint2 result=out_tile[wave*G::OUT_STRIDE+column];
-            const int x=x0+column,y=out_begin+G::GROUP*cb+wave;
-            if ((x < W) && (STEADY || (y < H)))
+            const uintx2 tile=lds_read_at<uintx2>(out_entry);
+            const uint2 result=make_uint2(tile[0],tile[1]);
+            asm volatile("" : "+s"(destination_rows));             // (as source_rows)
+            auto store_row=[&]()
+            {
+              asm volatile("" : "+v"(dst_entry));                  // (as fetch_steady's offsets)
+              store_pixel16(reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(args.dst)+destination_rows+
+                dst_entry),result);
+            };
+            if constexpr (FULL)
+              store_row();
+            else if (__builtin_amdgcn_inverse_ballot_w64(live_columns))
+              store_row();
+            destination_rows+=group_bytes;
+          }
+        else if ((cb >= 0) && (cb < nblocks))
+          {
+            const uintx2 tile=lds_read_at<uintx2>(out_entry);
+            const uint2 result=make_uint2(tile[0],tile[1]);
+            const int x=x0+lane,y=out_begin+G::GROUP*cb+wave;
+            if ((x < W) && (y < H))
               store_pixel16(args.dst+pixel_index(y,W,x)*PX,result);
           }
       }
@@ -800,13 +966,22 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
       MH_HTRACE_MARK(8);
       ring_group=ring_group+1 == G::NR ? 0 : ring_group+1;
     };
-    // fill and drain in the one tested body, the steady state between them in its own
+    // fill and drain in the one tested body, the steady state between them in its own: that of this kind of item
     for (int g=0; g < walk_end; g++)
       {
         if (g == steady_begin)
-          for (; g < steady_end; g++)
-            iteration(std::true_type{},g);
-        iteration(std::false_type{},g);
+          {
+            if (__builtin_expect(steady_kind == STEADY_INTERIOR,1))
+              for (; g < steady_end; g++)
+                iteration(std::integral_constant<int,STEADY_INTERIOR>{},g);
+            else if (steady_kind == STEADY_EDGE)
+              for (; g < steady_end; g++)
+                iteration(std::integral_constant<int,STEADY_EDGE>{},g);
+            else
+              for (; g < steady_end; g++)
+                iteration(std::integral_constant<int,STEADY_RAGGED>{},g);
+          }
+        iteration(std::integral_constant<int,WALK_TESTED>{},g);
       }
   };
   dispatch_roles<Roles,0>(wave,walk);
