@@ -395,7 +395,9 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   // lasts as long as its slowest item.  Every thread of an edge item takes the clamped loads (1.02); an interior
   // item's walk tests nothing per lane.  (Loading the group at clamp(xs, 0, W-4) and picking clamp(xs+i, 0, W-1) out
   // of it with selects — two loads a thread — brought the edge items to 1.006, but its 24 selects and their branch in
-  // the middle of the staging chain cost every interior item 3 %: profiles/hybrid_item_balance.md.)
+  // the middle of the staging chain cost every interior item 3 %: profiles/hybrid_item_balance.md.  In the edge
+  // items' own steady body, two pairs of columns and eight selects under scalar masks are level with the four clamped
+  // loads, 1.04 either way: profiles/hybrid_edge_fetch_alpha_settle.md.)
   const bool edge_item=(xin0 < 0) || (xin0+4*G::GROUPS_PER_ROW > W);
   auto fetch=[&](int g,int srow,int sxg)
   {
@@ -779,7 +781,8 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
                 todo=0ull;
               asm volatile("" : "+s"(todo));
               if (__builtin_expect(todo != 0ull,0))
-                recomputed+=settle_doubtful_pixels<false,4>(((todo >> lane) & 1ull) != 0ull,lane,args.taps64,K,
+                // (counted in pixels: a lane's four levels are four rows of its column, settled together)
+                recomputed+=4u*settle_doubtful_pixels<false,4>(((todo >> lane) & 1ull) != 0ull,lane,args.taps64,K,
                   fetch_alpha,q);
             }
             // the levels as the column pass's alpha samples (level/2: hi + lo is exact)
