@@ -243,7 +243,7 @@ MhStatus launch_separable_exact(const View &src,const View &dst,const MhKernelIn
     return MH_OK;
   const size_t n=(size_t) src.columns*src.rows;
   // two launches (premultiply inside the row pass, this file's finish step inside the column
-  // pass: convolve.hip) and one 32-byte-per-pixel intermediate where both axes have three taps
+  // pass: convolve_folded.hip) and one 32-byte-per-pixel intermediate where both axes have three taps
   const bool folded=(kw >= 3) && (kh >= 3) && (option("MAGICKHIP_NO_SEPARABLE_FOLD") == nullptr);
   Temp memory,table;
   // (folded: + the queue of undecided samples, at most 4 M entries; what overflows it is settled

@@ -57,21 +57,28 @@ static inline auto dispatch_colour_layout(MhQuantumKind quantum,int channels,F &
   return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
 }
 
-// ... with BLEND = blend where the last channel can be an alpha (C = 2 or 4): <Q,1,true> and
-// <Q,3,true> are never instantiated.
+// f(Layout<Q,C,BLEND>{}) for a Quantum type the caller has fixed, with BLEND = blend where the last
+// channel can be an alpha (C = 2 or 4): <Q,1,true> and <Q,3,true> are never instantiated.
+template<typename Q,class F>
+static inline auto dispatch_channels_blend(int channels,bool blend,F &&f)
+{
+  return dispatch_channels(channels,[&](auto c)
+  {
+    if constexpr ((c.value == 2) || (c.value == 4))
+      {
+        if (blend)
+          return f(Layout<Q,c.value,true>{});
+      }
+    return f(Layout<Q,c.value>{});
+  });
+}
+
+// ... and with Q from the run-time Quantum kind
 template<class F>
 static inline auto dispatch_layout_blend(MhQuantumKind quantum,int channels,bool blend,F &&f)
 {
-  return dispatch_layout(quantum,channels,[&](auto L)
-  {
-    using Q=typename decltype(L)::Q;
-    if constexpr ((L.C == 2) || (L.C == 4))
-      {
-        if (blend)
-          return f(Layout<Q,L.C,true>{});
-      }
-    return f(L);
-  });
+  return quantum == MH_QUANTUM_U16 ? dispatch_channels_blend<uint16_t>(channels,blend,f) :
+    dispatch_channels_blend<float>(channels,blend,f);
 }
 
 // ------------------------------------------------------------ pointwise streams

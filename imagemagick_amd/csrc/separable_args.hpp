@@ -1,4 +1,4 @@
-// The arguments of convolve_separable.hip's finish step, shared with the folded passes of convolve.hip.
+// The arguments of convolve_separable.hip's finish step, shared with the folded passes of convolve_folded.hip.
 #pragma once
 #include "mh_internal.hpp"
 
@@ -29,7 +29,7 @@ struct SeparableArgs
   unsigned queue_capacity;
 };
 
-// convolve.hip: the row pass (premultiply inside) and the column pass (finish inside) as two launches
+// convolve_folded.hip: the row pass (premultiply inside) and the column pass (finish inside) as two launches
 MhStatus launch_separable_folded(const View &src,const SeparableArgs &sep,const Conv1DParams &horizontal,
   const Conv1DParams &vertical,bool blend);
 

@@ -2940,7 +2940,7 @@ def convolve_every_layout(im, refmod, kernel, dtype, channels, alpha, precision,
 @pytest.mark.parametrize("dtype,channels,alpha", BLEND_LAYOUTS)
 @pytest.mark.parametrize("folded", [True, False])
 def test_separable_2d_convolve_exact_every_layout(im, refmod, dtype, channels, alpha, folded, options):
-    """convolve.hip's folded passes and convolve_separable.hip's four launches; with test_separable_2d_convolve_exact's
+    """convolve_folded.hip's passes and convolve_separable.hip's four launches; with test_separable_2d_convolve_exact's
     layouts, gray + alpha without alpha weighting."""
     options.set("MAGICKHIP_NO_EXACT_2D", "1")
     if not folded:
