@@ -4,6 +4,7 @@
 #pragma once
 #include "mh_internal.hpp"
 #include "device_common.hpp"
+#include "layout_dispatch.hpp"
 #include "conv1d_accum.hpp"
 #include <vector>
 
@@ -331,23 +332,15 @@ static inline Conv1DArgs conv1d_args(const View &src,const View &dst,const Conv1
   return args;
 }
 
-// One pass under its profile label.  More than 64 KB of dynamic LDS needs the attribute (set per launch), more
-// than the CU's 160 KB is refused.
+// One pass under its profile label (launch_dynamic_lds, layout_dispatch.hpp); more than the CU's 160 KB is refused.
 template<class... MORE>
 static MhStatus launch_with_dynamic_lds(const char *label,void (*kernel)(Conv1DArgs,MORE...),unsigned grid,
   unsigned block,size_t lds,hipStream_t stream,const Conv1DArgs &args,MORE... more)
 {
   if (lds > 160u*1024u)
     return fail(MH_UNSUPPORTED,"row kernel of %d taps needs %zu bytes of LDS",args.ntaps,lds);
-  if (lds > 64u*1024u)
-    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int) lds));
-  {
-    ProfileScope prof(label,stream);
-    hipLaunchKernelGGL(kernel,dim3(grid),dim3(block),lds,stream,args,more...);
-  }
-  MH_HIP(hipGetLastError());
-  return MH_OK;
+  ProfileScope prof(label,stream);
+  return launch_dynamic_lds(kernel,dim3(grid),dim3(block),lds,stream,args,more...);
 }
 
 } // namespace mh

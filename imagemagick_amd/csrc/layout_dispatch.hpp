@@ -1,6 +1,7 @@
 // Host-side helpers of the kernel launchers: the run-time pixel layout (Quantum type, channel
-// count, alpha blending) turned into template arguments, the launch geometry of the pointwise
-// streams and that of the operators that stage a window in LDS for 16 x 16 outputs.
+// count, alpha blending) turned into template arguments, the launch with more than 64 KB of dynamic
+// LDS, the launch geometry of the pointwise streams, that of the one-thread-per-column operators and
+// that of the operators that stage a window in LDS for 16 x 16 outputs.
 #pragma once
 
 #include "mh_internal.hpp"
@@ -32,16 +33,22 @@ static inline auto dispatch_channels(int channels,F &&f)
   }
 }
 
-// f(Layout<Q,C>{}) with Q = uint16_t (MH_QUANTUM_U16) or float and C = channels, as above.
+// f(q) with a value q of the Quantum type: uint16_t (MH_QUANTUM_U16) or float.
+template<class F>
+static inline auto dispatch_quantum(MhQuantumKind quantum,F &&f)
+{
+  return quantum == MH_QUANTUM_U16 ? f(uint16_t{}) : f(float{});
+}
+
+// f(Layout<Q,C>{}) with Q as above and C = channels, as above.
 template<class F>
 static inline auto dispatch_layout(MhQuantumKind quantum,int channels,F &&f)
 {
-  const auto typed=[&](auto q)
+  return dispatch_quantum(quantum,[&](auto q)
   {
     using Q=decltype(q);
     return dispatch_channels(channels,[&](auto c) { return f(Layout<Q,c.value>{}); });
-  };
-  return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
+  });
 }
 
 // ... for the kernels that exist for R,G,B[,A] frames only: f receives Layout<Q,3> or Layout<Q,4>
@@ -49,12 +56,11 @@ static inline auto dispatch_layout(MhQuantumKind quantum,int channels,F &&f)
 template<class F>
 static inline auto dispatch_colour_layout(MhQuantumKind quantum,int channels,F &&f)
 {
-  const auto typed=[&](auto q)
+  return dispatch_quantum(quantum,[&](auto q)
   {
     using Q=decltype(q);
     return channels == 3 ? f(Layout<Q,3>{}) : f(Layout<Q,4>{});
-  };
-  return quantum == MH_QUANTUM_U16 ? typed(uint16_t{}) : typed(float{});
+  });
 }
 
 // f(Layout<Q,C,BLEND>{}) for a Quantum type the caller has fixed, with BLEND = blend where the last
@@ -77,8 +83,21 @@ static inline auto dispatch_channels_blend(int channels,bool blend,F &&f)
 template<class F>
 static inline auto dispatch_layout_blend(MhQuantumKind quantum,int channels,bool blend,F &&f)
 {
-  return quantum == MH_QUANTUM_U16 ? dispatch_channels_blend<uint16_t>(channels,blend,f) :
-    dispatch_channels_blend<float>(channels,blend,f);
+  return dispatch_quantum(quantum,[&](auto q) { return dispatch_channels_blend<decltype(q)>(channels,blend,f); });
+}
+
+// ------------------------------------------------------------ dynamic LDS
+// One launch and its check.  More than 64 KB of dynamic LDS needs the attribute (set per launch).
+template<class... PARAMS,class... ARGS>
+static MhStatus launch_dynamic_lds(void (*kernel)(PARAMS...),dim3 grid,dim3 block,size_t lds,hipStream_t stream,
+  const ARGS &...args)
+{
+  if (lds > 64u*1024u)
+    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),hipFuncAttributeMaxDynamicSharedMemorySize,
+      (int) lds));
+  hipLaunchKernelGGL(kernel,grid,block,lds,stream,args...);
+  MH_HIP(hipGetLastError());
+  return MH_OK;
 }
 
 // ------------------------------------------------------------ pointwise streams
@@ -95,6 +114,16 @@ static unsigned stream_grid(size_t npixels)
   if (blocks < 1)
     blocks=1;
   return (unsigned) blocks;
+}
+
+// ------------------------------------------------------------ one thread per column
+// The operators of effects.hip: a thread per column (or per padded column, per column and colour channel, per sample
+// of a flat array), kColumnBlock threads a block, a grid row per image row.
+constexpr int kColumnBlock=256;
+
+static inline dim3 column_grid(size_t columns,size_t rows=1)
+{
+  return dim3((unsigned) ((columns+kColumnBlock-1)/kColumnBlock),(unsigned) rows);
 }
 
 // ------------------------------------------------------------ 16 x 16 outputs per workgroup

@@ -341,6 +341,10 @@ struct Morph2DParams
 };
 MhStatus launch_morph2d(const View &src,const View &dst,const Morph2DParams &params,
   const Roles &roles,unsigned long long *changed_device);
+// ... Erode / Dilate of launch_morph2d's cell list by a flat kernel (morphology_flat.hip), or *handled = false
+struct Cell;
+MhStatus launch_morph_flat(const View &src,const View &dst,bool dilate,const Cell *cells,size_t ncells,
+  const Roles &roles,unsigned long long *changed_device,bool *handled);
 
 struct TapTable;   // resize contribution table (host), see resize_filter.cpp
 MhStatus launch_resize_pass(const View &src,const View &dst,bool vertical,

@@ -1,6 +1,6 @@
 // Pointwise kernels of no larger family: CompositeImage, ContrastImage / ModulateImage (HSB, HSL), GrayscaleImage,
 // FunctionImage, the gray scan, the unsharp-mask epilogue, and the layout helpers of operators.cpp and
-// morphology.hip: premultiply / separable finish, gray row bands, RGB pad / unpad and a plain copy.
+// morphology_flat.hip: premultiply / separable finish, gray row bands, RGB pad / unpad and a plain copy.
 //
 // All of these stream every pixel once (HBM-bound): lanes take consecutive
 // pixels with the widest load the pixel size allows, grid-stride over the
@@ -705,7 +705,7 @@ MhStatus launch_gray_bands_unpack(const View &packed,const View &dst,int band,in
 
 // ------------------------------------------------------------------ three-channel frames with a fourth, empty one
 // RGB without alpha — 6-byte (Q16) or 12-byte (float) pixels — has no vector load of its own either; the
-// union-of-rectangles kernel (morphology.hip) takes 8- and 16-byte pixels.  Padded to four channels (the fourth 0) it
+// union-of-rectangles kernel (morphology_flat.hip) takes 8- and 16-byte pixels.  Padded to four channels (the fourth 0) it
 // is an ordinary four-channel frame; minima and maxima are per channel.
 template<typename Q>
 __global__ __launch_bounds__(256)

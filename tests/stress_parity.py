@@ -160,7 +160,7 @@ def check(name, got, want, limit, detail):
 NUMBER_OF_OPS = 26
 
 # families 16 to 18: cases the library declined / cases run, per family.  A declined case passes only when the decline
-# condition stated in morphology.hip holds for it, and at most a quarter of a family's cases may be declined.
+# condition stated in effects.hip holds for it, and at most a quarter of a family's cases may be declined.
 declined = {}
 drawn = {}
 
@@ -244,7 +244,7 @@ def draw_enhance_case(op):
             # a blur width from below 1 (declined) to a little above half the columns (declined from (columns-2)/2 on)
             longest = max(rows, cols)
             radius = float(rng.uniform(0.7, 0.55 * cols)) / (0.002 * longest) * (1.0 if rng.random() < 0.8 else -1.0)
-            w = int(longest * 0.002 * abs(radius))                   # launch_local_contrast, morphology.hip
+            w = int(longest * 0.002 * abs(radius))                   # launch_local_contrast, effects.hip
             case.update(name="local_contrast", args=(radius, float(rng.uniform(-100.0, 100.0))),
                         declines=(w < 1) or (cols <= 2 * w + 2))
         elif which == 1:

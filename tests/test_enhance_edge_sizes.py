@@ -1,6 +1,6 @@
 """Keeps the big-frame and block-boundary cases of tests/test_gpu_enhance_edges.py honest without a GPU: their sizes
 follow constants of the kernels' sources (stream_grid's block cap, the 256-thread block, kPointBatch), read here from
-layout_dispatch.hpp, pointwise.hip and morphology.hip the way the *_kernel_resources modules read ISA facts.  Whoever changes one of them
+layout_dispatch.hpp, pointwise.hip and effects.hip the way the *_kernel_resources modules read ISA facts.  Whoever changes one of them
 gets a failure here instead of a GPU test that quietly stops covering the second trip of a grid-stride loop.  Also
 draws the first cases of the stress families 16 to 18 (no GPU needed: the decline conditions depend on shape and
 radius only) and checks the share of declined cases against the quarter the driver allows."""
@@ -71,25 +71,41 @@ def test_big_frames_sit_just_above_one_trip_of_the_grid_stride_loops():
     assert edges.GUARD_ROWS * edges.BIG_TONE_SHAPE[1] >= width * batch        # what a batch could overrun stays inside the guard
 
 
+def column_constants():
+    """kColumnBlock and the one-thread-per-column grid of layout_dispatch.hpp."""
+    geometry = source("layout_dispatch.hpp")
+    block = re.search(r"constexpr int kColumnBlock=(\d+);", geometry)
+    assert block
+    grid = function_body(geometry, "static inline dim3 column_grid(size_t columns,size_t rows=1)")
+    assert "return dim3((unsigned) ((columns+kColumnBlock-1)/kColumnBlock),(unsigned) rows);" in grid
+    return int(block.group(1))
+
+
 def test_block_boundary_widths_follow_the_kernels_block_width():
-    text = source("morphology.hip")
+    text = source("effects.hip")
     kernels = ["motion_blur_kernel", "rotational_blur_kernel", "local_contrast_luma_kernel", "local_contrast_vertical_kernel",
                "local_contrast_horizontal_kernel", "despeckle_load_kernel", "hull_kernel", "despeckle_store_kernel",
                "wavelet_hat_kernel"]
     widths = {kernel_launch_bounds(text, k) for k in kernels}
     assert widths == {edges.BLOCK_WIDTH}
     b = edges.BLOCK_WIDTH
+    assert column_constants() == b                        # the launchers' block is the kernels' launch bound
     # the launches: one thread per column (despeckle_load: per padded column, wavelet_hat: per column and colour channel)
-    assert "dim3 grid((unsigned) ((a.columns+%d)/%d),(unsigned) a.rows),block(%d);" % (b - 1, b, b) in function_body(
-        text, "static MhStatus motion_typed(")
-    assert "dim3 grid((unsigned) ((a.columns+%d)/%d),(unsigned) a.rows),block(%d);" % (b - 1, b, b) in function_body(
-        text, "MhStatus launch_rotational_blur(")
+    motion = function_body(text, "MhStatus launch_motion_blur(")
+    assert "column_grid(a.columns,a.rows)" in motion and "dim3(kColumnBlock)" in motion and "motion_blur_kernel<" in motion
+    rotational = function_body(text, "MhStatus launch_rotational_blur(")
+    assert "column_grid(a.columns,a.rows)" in rotational and "dim3(kColumnBlock)" in rotational
+    assert "rotational_blur_kernel<" in rotational
     local = function_body(text, "MhStatus launch_local_contrast(")
-    assert "const dim3 block(%d);" % b in local and "gx=(unsigned) ((a.columns+%d)/%d);" % (b - 1, b) in local
+    assert "const dim3 block(kColumnBlock),grid=column_grid(a.columns,a.rows);" in local
+    assert "column_grid(a.columns,a.rows+2*a.w),block" in local
     despeckle = function_body(text, "static MhStatus despeckle_typed(")
-    assert "const dim3 block(%d);" % b in despeckle and "(W+2+%d)/%d" % (b - 1, b) in despeckle and "(W+%d)/%d" % (b - 1, b) in despeckle
+    assert "const dim3 block(kColumnBlock);" in despeckle and "column_grid(W+2,H+2),block" in despeckle
+    assert "const dim3 grid=column_grid(W,H);" in despeckle
     wavelet = function_body(text, "MhStatus launch_wavelet_denoise(")
-    assert "const dim3 block(%d);" % b in wavelet and "(W*colour+%d)/%d" % (b - 1, b) in wavelet
+    assert "const dim3 block(kColumnBlock);" in wavelet and "const dim3 grid=column_grid(W*colour,H);" in wavelet
+    # no launch of these files' kernels with a block or grid spelled by hand
+    assert not re.search(r"block\(\d+\)|dim3\(\d+\)|\+\d+\)/\d+", text)
     w = edges.BOUNDARY_WIDTHS
     assert {b - 1, b, b + 1} <= set(w)                    # one below, on and one above a block
     assert 2 * b + 1 in w and any(b + 1 < v < 2 * b for v in w)      # a third block of one column; a ragged second block

@@ -1,6 +1,6 @@
 """Edge shapes, channel masks, alpha structure, float specials and both precisions for the nine enhance / effect
 operators that had one small random frame each: MotionBlurImage, RotationalBlurImage, LocalContrastImage,
-DespeckleImage, WaveletDenoiseImage (morphology.hip: one thread per column, 256-thread blocks) and ContrastImage,
+DespeckleImage, WaveletDenoiseImage (effects.hip: one thread per column, 256-thread blocks) and ContrastImage,
 ModulateImage, FunctionImage, GrayscaleImage (pointwise.hip: grid-stride loops under stream_grid's block cap).
 
 Every case goes through the C ABI and is compared with the compiled reference (oracle/_ref) on the same input.
@@ -76,7 +76,7 @@ def local_contrast_width(rows, cols, radius):
 
 
 def declines(name, rows, cols, args):
-    """The decline conditions stated in morphology.hip (launch_wavelet_denoise, launch_local_contrast)."""
+    """The decline conditions stated in effects.hip (launch_wavelet_denoise, launch_local_contrast)."""
     if name == "wavelet":
         return rows < 33 or cols < 33
     if name == "local_contrast":
@@ -86,7 +86,7 @@ def declines(name, rows, cols, args):
 
 
 def run_morph(im, refmod, name, px, args=None, mask=None, copy=(), host=False, what=""):
-    """One of the five morphology.hip operators on `px` against the reference; a frame the library is documented to
+    """One of the five effects.hip operators on `px` against the reference; a frame the library is documented to
     decline must raise, any other must match."""
     fn, method, default = MORPH_OPS[name]
     args = default if args is None else args

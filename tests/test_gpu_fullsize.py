@@ -99,7 +99,7 @@ def test_gray_blur_and_unsharp_full_size_take_the_four_band_form(im, refmod):
     small = im.Image(to_device(px[:1024, :1024].copy()))
     launched = set(bench.kernel_profile(im, lambda: holder.update(s=im.blur_image(small, 0.0, 10.0)), 1))
     assert "gray_bands_pack" not in launched, launched
-    # ... and Erode / Dilate Disk:15 through the union-of-rectangles kernel (morphology.hip try_rects_gray_bands)
+    # ... and Erode / Dilate Disk:15 through the union-of-rectangles kernel (morphology_flat.hip morph_rects_gray_bands)
     for method in ("Dilate", "Erode"):
         launched = set(bench.kernel_profile(im, lambda: holder.update(m=im.morphology_image(image, method, 1, "Disk:15")), 1))
         assert launched == {"gray_bands_pack", "morph_rects", "gray_bands_unpack"}, launched

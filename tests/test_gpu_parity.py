@@ -972,7 +972,7 @@ def test_gray_convolve_2d_as_four_row_bands(im, refmod, what, rows, options):
 def test_rgb_erode_dilate_with_a_fourth_empty_channel(im, refmod, dtype, method, kernel, iterations, options):
     """Erode / Dilate (and the compound methods built on them) on a three-channel frame — RGB without alpha, what
     most photographs are, 6- or 12-byte pixels: padded to four channels for the union-of-rectangles kernel
-    (morphology.hip try_rects_rgb_padded; the fourth channel is empty and dropped again, the change count that
+    (morphology_flat.hip morph_rects_rgb_padded; the fourth channel is empty and dropped again, the change count that
     ends an unbounded iteration is taken on the way, morphology.c:3195-3199).  Bit-identical to the reference
     and to the form it replaces; values below zero and beyond the Quantum range on float frames."""
     import bench
@@ -1039,7 +1039,7 @@ def test_rgb_padded_erode_with_a_channel_mask(im, refmod, dtype, options):
 def test_gray_erode_dilate_as_four_row_bands(im, refmod, method, kernel, iterations, rows, options):
     """Erode / Dilate (and the compound methods built on them) on a one-channel Q16 frame — the masks these
     operators are mostly run on: the frame's rows as four bands = the four channels of a frame a quarter as tall,
-    through the union-of-rectangles kernel (morphology.hip try_rects_gray_bands).  Heights that are and are not
+    through the union-of-rectangles kernel (morphology_flat.hip morph_rects_gray_bands).  Heights that are and are not
     multiples of four, kernels whose origin is not their middle row, bands barely taller than the kernel's reach
     (the form declines below that), an unbounded iteration that ends on the change count taken while unpacking
     (morphology.c:3199, :3634-4077).  Bit-identical to the reference and to the form it replaces."""
@@ -1069,6 +1069,35 @@ def test_gray_erode_dilate_as_four_row_bands(im, refmod, method, kernel, iterati
     options.set("MAGICKHIP_NO_GRAY_BANDS", "1")
     assert_parity(im.morphology_image(dev, method, iterations, kernel).numpy(), want, True,
                   "gray %s %s (the frame's own form)" % (method, kernel))
+
+
+@pytest.mark.parametrize("kernel", [
+    "5x3: nan,nan,1,nan,nan nan,1,1,1,nan 1,1,1,1,1",
+    "7x4+3+1: nan,nan,1,1,1,nan,nan nan,1,1,1,1,1,nan 1,1,1,1,1,1,1 1,1,1,1,1,1,1",
+])
+@pytest.mark.parametrize("channels,dtype,option_names", [
+    (1, Q16, ("MAGICKHIP_GRAY_BANDS_MIN_PIXELS",)),
+    (3, Q16, ("MAGICKHIP_RGB_PAD_MIN_PIXELS",)),
+    (3, HDRI, ("MAGICKHIP_RGB_PAD_MIN_PIXELS", "MAGICKHIP_RGB_PAD_FLOAT_ALWAYS")),
+])
+def test_one_sided_kernels_are_routed_before_anything_is_packed(im, refmod, kernel, channels, dtype, option_names, options):
+    """Centred runs that narrow to one side only (a triangle of 1, 3 and 5 cells; a trapezoid of four rows with its
+    origin on an inner row) pass every test of morph_convex_kernel and none of the union-of-rectangles kernel's: the
+    route (morphology_flat.hip launch_morph_flat) is known from the kernel's shape before a gray frame is cut into bands or
+    an RGB frame padded, so neither happens.  Two convex tiles each way; bit-identical to the reference."""
+    import bench
+    options.set(option_names[0], "0")
+    for name in option_names[1:]:
+        options.set(name, "1")
+    px = make_pixels(64, 96, channels, dtype, seed=channels + len(kernel))
+    dev, ref = run_pair(im, refmod, px)
+    for method in ("Erode", "Dilate"):
+        holder = {}
+        launched = set(bench.kernel_profile(im, lambda: holder.update(out=im.morphology_image(dev, method, 1, kernel)), 1))
+        assert_parity(holder["out"].numpy(), ref.morphology(method, 1, kernel).numpy(), True,
+                      "%s %s, %d channels %s" % (method, kernel, channels, dtype))
+        assert "morph_convex" in launched, launched
+        assert not launched & {"gray_bands_pack", "gray_bands_unpack", "rgb_pad", "rgb_unpad", "morph_rects"}, launched
 
 
 @pytest.mark.parametrize("channels", [4, 2, 1])

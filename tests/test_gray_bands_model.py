@@ -1,4 +1,4 @@
-"""The geometry of the four-row-band form (operators.cpp fused_blur_gray_bands, morphology.hip try_rects_gray_bands,
+"""The geometry of the four-row-band form (operators.cpp fused_blur_gray_bands, morphology_flat.hip morph_rects_gray_bands,
 pointwise.hip gray_bands_pack_kernel / gray_bands_unpack_kernel), restated in NumPy: a one-channel frame's rows cut into
 four bands = the four channels of a frame a quarter as tall, `halo` extra rows either side of every band, the frame's
 edge rows repeated above the first and below the last band.  Any translation-invariant stencil that clamps at the edges

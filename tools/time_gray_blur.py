@@ -1,5 +1,5 @@
 """One-channel (gray) Q16 BlurImage / UnsharpMaskImage / Erode / Dilate: the frame's own kernels against the four-row-band
-form (operators.cpp fused_blur_gray_bands, morphology.hip try_rects_gray_bands), ms per call, FAST and EXACT.
+form (operators.cpp fused_blur_gray_bands, morphology_flat.hip morph_rects_gray_bands), ms per call, FAST and EXACT.
     python tools/time_gray_blur.py [sigma,sigma,...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Erode / Dilate on RGBA, RGB (6-byte pixels: padded to four channels, morphology.hip try_rects_rgb_padded) and two plain
+"""Erode / Dilate on RGBA, RGB (6-byte pixels: padded to four channels, morphology_flat.hip morph_rects_rgb_padded) and two plain
 channels, Q16 and float RGB, ms per call and the kernels that ran.   python tools/time_rgb_morphology.py"""
 import sys
 import os
