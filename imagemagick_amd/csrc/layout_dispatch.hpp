@@ -86,6 +86,17 @@ static inline auto dispatch_layout_blend(MhQuantumKind quantum,int channels,bool
   return dispatch_quantum(quantum,[&](auto q) { return dispatch_channels_blend<decltype(q)>(channels,blend,f); });
 }
 
+// ... for the kernels of four-channel frames only: f receives Layout<Q,4,false> or Layout<Q,4,true>
+template<class F>
+static inline auto dispatch_rgba_blend(MhQuantumKind quantum,bool blend,F &&f)
+{
+  return dispatch_quantum(quantum,[&](auto q)
+  {
+    using Q=decltype(q);
+    return blend ? f(Layout<Q,4,true>{}) : f(Layout<Q,4,false>{});
+  });
+}
+
 // ------------------------------------------------------------ dynamic LDS
 // One launch and its check.  More than 64 KB of dynamic LDS needs the attribute (set per launch).
 template<class... PARAMS,class... ARGS>

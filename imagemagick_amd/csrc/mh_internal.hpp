@@ -113,7 +113,7 @@ MhStatus upload_table(Temp &dst,int device,hipStream_t stream,const void *host,s
 MhStatus shared_table(int device,hipStream_t stream,const void *host,size_t bytes,const void **device_ptr,
   std::shared_ptr<void> *keep=nullptr);
 void release_shared_tables();       // MhTerminus
-void release_resize_tables();       // the resize launchers' device-side tables (resize.hip)
+void release_resize_tables();       // the resize launchers' device-side tables and plans (resize.hip)
 void release_batch_streams();       // the worker streams of batch.cpp (after the pools were trimmed)
 void release_rccl_communicators();  // batch.cpp's cached communicators
 
@@ -139,6 +139,65 @@ private:
   size_t total_=0;
   Temp block_;
 };
+
+// A bundle that calls on any stream of its device share (the resize launchers' cached tables and
+// plans): publish() uploads it on the builder's stream, wait() puts another call's stream behind
+// that upload.
+struct DeviceTables
+{
+  TableBundle tables;
+  hipEvent_t ready=nullptr;          // the upload, for callers on another stream
+  int device=-1;
+  DeviceTables() = default;
+  DeviceTables(const DeviceTables &) = delete; DeviceTables &operator=(const DeviceTables &) = delete;
+  MhStatus publish(int on_device,hipStream_t stream)
+  {
+    MH_TRY(tables.upload(on_device,stream));
+    device=on_device;
+    MH_HIP(hipEventCreateWithFlags(&ready,hipEventDisableTiming));
+    MH_HIP(hipEventRecord(ready,stream));
+    return MH_OK;
+  }
+  MhStatus wait(hipStream_t stream) const      // (nothing to wait for before publish())
+  {
+    if (ready != nullptr)
+      MH_HIP(hipStreamWaitEvent(stream,ready,0));
+    return MH_OK;
+  }
+  ~DeviceTables()
+  {
+    // The tables are shared across streams; their block goes back to a pool that tags it with
+    // the BUILDER's stream only.  Evictions are rare (more geometries in flight than the cache
+    // holds): wait for the device, so that no kernel of another stream can still be reading them.
+    if (device >= 0)
+      {
+        DeviceGuard guard;
+        if (guard.enter(device) == hipSuccess)
+          (void) hipDeviceSynchronize();
+      }
+    if (ready != nullptr)
+      (void) hipEventDestroy(ready);
+  }
+};
+
+// *out = the DeviceTables-derived value `cache` (an MruCache, mru_cache.hpp) has under `key`, with
+// `stream` behind its upload, or one that build(value) fills, outside the cache's lock, and the
+// cache then keeps.  keep = false: built for this call only.
+template<class Cache,class Key,class Value,class Build>
+static MhStatus acquire_device_tables(Cache &cache,const Key &key,bool keep,hipStream_t stream,
+  std::shared_ptr<Value> *out,Build &&build)
+{
+  if (keep && (*out=cache.find(key)))
+    return (*out)->wait(stream);
+  *out=std::make_shared<Value>();
+  MH_TRY(build(**out));
+  // (what the cache evicts for it is let go of on return, outside the cache's lock: a destructor
+  // that drains the device must not hold up the other threads' lookups)
+  std::shared_ptr<Value> evicted;
+  if (keep)
+    evicted=cache.insert(key,*out);
+  return MH_OK;
+}
 
 // Resolved, device-resident view of an MhImage for the kernel launchers.
 struct View

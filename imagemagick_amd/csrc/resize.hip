@@ -25,8 +25,10 @@
 //              taps, so the reads broadcast).
 #include "mh_internal.hpp"
 #include "resize_filter.hpp"
+#include "resize_pass_plan.hpp"
+#include "layout_dispatch.hpp"
+#include "mru_cache.hpp"
 #include <memory>
-#include <mutex>
 #include "device_common.hpp"
 #include "resize_acc.hpp"
 #include <cstdlib>
@@ -261,13 +263,11 @@ void resize_horizontal_kernel(ResizeArgs args,int tile_rows)
 // Quantum->double conversion costs as much issue time as a multiply-add), and
 // every lane runs the same number of taps (the tile's maximum; the extra taps
 // carry zero weights) so the tap loop has no per-lane predicates.
-template<typename Q,int C,bool BLEND,class A,int MAXT,bool PREMUL=false>
+template<typename Q,int C,bool BLEND,class A,int MAXT>
 __global__ __launch_bounds__(256)
 void resize_horizontal_cvt_kernel(ResizeArgs args,int tile_rows,int lds_span)
 {
   typedef typename A::T T;
-  // PREMUL (Fma64, alpha-weighted, every channel updated): the tile holds alpha*colour, alpha
-  static_assert(!PREMUL || ResizeAcc<Q,C,BLEND,A>::kDerive,"premultiplied staging needs the derived gamma");
   // Zero-weight padding taps (j >= count) multiply a sample OUTSIDE the output's window by 0: an
   // exact no-op unless that sample is not finite (0*inf = NaN where the reference never looks,
   // resize.c:3494-3530).  EXACT on a float frame tests every tap; FAST on a float frame looks at
@@ -325,10 +325,9 @@ void resize_horizontal_cvt_kernel(ResizeArgs args,int tile_rows,int lds_span)
         for (int k=0; k < BATCH; k++)
           if (i0+256*k < items)
             {
-              const T scale=PREMUL ? (T) v[k][C-1] : (T) 1;
 #pragma unroll
               for (int c=0; c < C; c++)
-                tile[(size_t) slot[k]*C+c]=(PREMUL && (c != C-1)) ? scale*(T) v[k][c] : (T) v[k][c];
+                tile[(size_t) slot[k]*C+c]=(T) v[k][c];
             }
       }
   }
@@ -377,12 +376,7 @@ void resize_horizontal_cvt_kernel(ResizeArgs args,int tile_rows,int lds_span)
 #pragma unroll
       for (int j=0; j < MAXT; j++)
         if (!careful || (j < count))              // zero-weight taps are exact no-ops on finite samples
-          {
-            if constexpr (PREMUL)
-              acc.tap_premultiplied(w[j],p[j]);
-            else
-              acc.tap_converted(w[j],wq[j],p[j]);
-          }
+          acc.tap_converted(w[j],wq[j],p[j]);
       Q copy[C],out[C];
 #pragma unroll
       for (int c=0; c < C; c++)
@@ -405,12 +399,13 @@ MhStatus launch_resize_fused(const View &src,const View &dst,const TapTable &ver
   const TapTable &horizontal,const Roles &roles,MhPrecision prec,bool *handled)
 {
   *handled=false;
-  if ((src.channels != dst.channels) || (src.quantum != dst.quantum))
-    return fail(MH_BAD_ARGUMENT,"resize: layout mismatch");
-  if (roles.blend && (roles.alpha != src.channels-1))
-    return MH_OK;
-  if (((int) dst.rows != vertical.out_size) || ((int) dst.columns != horizontal.out_size))
-    return fail(MH_BAD_ARGUMENT,"resize: geometry mismatch");
+  switch (resize_front_check(src,dst,vertical,horizontal,roles))
+  {
+    case RESIZE_FRONT_LAYOUT: return fail(MH_BAD_ARGUMENT,"resize: layout mismatch");
+    case RESIZE_FRONT_ALPHA_NOT_LAST: return MH_OK;
+    case RESIZE_FRONT_GEOMETRY: return fail(MH_BAD_ARGUMENT,"resize: geometry mismatch");
+    case RESIZE_FRONT_OK: break;
+  }
   // The one-launch forms are FAST forms (fused multiply-adds, derived gamma: within one ULP / one
   // level).  (Rounds 1 and 2 had two EXACT-capable forms that kept the intermediate tile in LDS and
   // cost as much as the two passes together — 8.6 and 6.0 ms on config C3; removed in round 5,
@@ -443,236 +438,154 @@ MhStatus launch_resize_fused(const View &src,const View &dst,const TapTable &ver
 
 // ---------------------------------------------------------------- launcher
 // Everything a resize pass reads besides the pixels, resident on the device: the contribution
-// lists, the per-tile dense weight matrices of the vertical kernel or the per-tile spans of the
-// horizontal one, and the launch geometry that follows from them.  Built once per (contribution
-// table, axis, weight type) and kept (a pass of config C3 uploads 4 MB: 70-140 us of idle GPU in
-// front of a 1.3 ms kernel, and ~0.5 ms of host loops per call).
-struct PassTables
+// lists its kernel looks at and the per-tile dense weight matrices of the vertical kernel or the
+// per-tile spans of the horizontal one (resize_pass_plan.hpp).  Built once per (contribution table,
+// axis) and kept (a pass of config C3 uploads 4 MB: 70-140 us of idle GPU in front of a 1.3 ms
+// kernel, and ~0.5 ms of host loops per call).
+struct PassTables : DeviceTables
 {
-  TableBundle tables;
-  size_t i_start=0,i_count=0,i_near=0,i_w=0,i_wq=0;
-  // vertical: dense W[tile][k][RY]
+  size_t i_count=0,i_near=0;
+  // vertical: dense W[tile][k][kVerticalRows]
   size_t i_lo=0,i_rows=0,i_mask=0,i_dw=0,i_dwq=0;
-  int tiles=0,kmax=1,ry=0;
-  // horizontal: per 256-column tile
-  size_t i_tile_lo=0,i_tile_span=0;
-  int max_span=1,overhang=0,maxt=8;
-  hipEvent_t ready=nullptr;          // the upload, for callers on another stream
-  int device=-1;
-  ~PassTables()
-  {
-    // The tables are shared across streams; their block goes back to a pool that tags it with
-    // the BUILDER's stream only.  Evictions are rare (more than eight geometries in flight):
-    // wait for the device, so that no kernel of another stream can still be reading them.
-    if (device >= 0)
-      {
-        DeviceGuard guard;
-        if (guard.enter(device) == hipSuccess)
-          (void) hipDeviceSynchronize();
-      }
-    if (ready != nullptr)
-      (void) hipEventDestroy(ready);
-  }
+  int tiles=0,kmax=1;
+  // horizontal: the lists' starts and weights, per 256-column tile its span
+  size_t i_start=0,i_w=0,i_wq=0,i_tile_lo=0,i_tile_span=0;
+  HorizontalSpans spans;
 };
 
-#ifndef MH_VERTICAL_ROWS
-#define MH_VERTICAL_ROWS 4
-#endif
-constexpr int kVerticalRows=MH_VERTICAL_ROWS;      // output rows per tile of resize_vertical_kernel
-// (A reduction's windows are long and overlap — 4x Lanczos: 25 source rows per output, consecutive outputs four
-// rows apart — so a tile of 4 outputs reads 40 rows for 16 new ones, the frame 2.5 times: the pass is bound by
-// that traffic, 0.27 ms for 8192^2 -> 8192x2048 Q16.  Sixteen outputs a tile read it 1.4 times but, in the dense
-// form, run 88 x 16 multiply-adds for 16 x 25 useful ones: 0.82 ms; profiles/r6_notes/resize_reduction.txt.)
-static inline int vertical_rows_of(const TapTable &)
-{
-  return kVerticalRows;
-}
+static_assert(kPassQuantumScale == kQuantumScale,"resize_pass_plan.hpp restates QuantumScale");
 
-template<typename T>
 static MhStatus build_pass_tables(PassTables &p,const TapTable &table,bool vertical,int device,
   hipStream_t stream)
 {
-  const size_t n=(size_t) table.max_taps*(size_t) table.out_size;
-  std::vector<T> w(n),wq(n);
-  for (size_t i=0; i < n; i++)
-    {
-      w[i]=(T) table.weight[i];
-      wq[i]=(T) (table.weight[i]*kQuantumScale);     // contribution.weight*QuantumScale
-    }
-  const size_t ib=(size_t) table.out_size*sizeof(int);
-  p.i_start=p.tables.add(table.start.data(),ib);
-  p.i_count=p.tables.add(table.count.data(),ib);
-  p.i_near=p.tables.add(table.nearest.data(),ib);
-  p.i_w=p.tables.add(w.data(),n*sizeof(T));
-  p.i_wq=p.tables.add(wq.data(),n*sizeof(T));
-  std::vector<int> lo,nrows,tile_lo,tile_span;
-  std::vector<double> dw,dwq;
-  std::vector<unsigned> mask;
+  const auto add=[&](const auto &v) { return p.tables.add(v.data(),v.size()*sizeof(v[0])); };
+  VerticalPassPlan v;                                // (host memory of the parts: until publish())
+  HorizontalPassPlan h;
+  p.i_count=add(table.count);
+  p.i_near=add(table.nearest);
   if (vertical)
     {
-      const int RY=vertical_rows_of(table);
-      p.ry=RY;
-      const int tiles=(table.out_size+RY-1)/RY;
-      lo.assign((size_t) tiles,0);
-      nrows.assign((size_t) tiles,0);
-      int kmax=1;
-      for (int t=0; t < tiles; t++)
-        {
-          int l=0x7fffffff,h=0;
-          for (int r=0; r < RY; r++)
-            {
-              int y=t*RY+r;
-              if ((y >= table.out_size) || (table.count[(size_t) y] <= 0))
-                continue;
-              int st=table.start[(size_t) y],en=st+table.count[(size_t) y];
-              l=st < l ? st : l;
-              h=en > h ? en : h;
-            }
-          if (h <= l)
-            { l=0; h=0; }
-          lo[(size_t) t]=l;
-          nrows[(size_t) t]=h-l;
-          kmax=(h-l) > kmax ? (h-l) : kmax;
-        }
-      dw.assign((size_t) tiles*kmax*RY,0.0);
-      dwq.assign((size_t) tiles*kmax*RY,0.0);
-      mask.assign((size_t) tiles*kmax,0u);
-      for (int t=0; t < tiles; t++)
-        for (int r=0; r < RY; r++)
-          {
-            int y=t*RY+r;
-            if ((y >= table.out_size) || (table.count[(size_t) y] <= 0))
-              continue;
-            for (int j=0; j < table.count[(size_t) y]; j++)
-              {
-                int k=table.start[(size_t) y]+j-lo[(size_t) t];
-                double wv=table.weight[(size_t) j*table.out_size+(size_t) y];
-                size_t at=((size_t) t*kmax+(size_t) k)*RY+(size_t) r;
-                dw[at]=wv;
-                dwq[at]=wv*kQuantumScale;       // contribution.weight*QuantumScale
-                mask[(size_t) t*kmax+(size_t) k]|=1u << r;
-              }
-          }
-      p.tiles=tiles;
-      p.kmax=kmax;
-      p.i_lo=p.tables.add(lo.data(),lo.size()*sizeof(int));
-      p.i_rows=p.tables.add(nrows.data(),nrows.size()*sizeof(int));
-      p.i_mask=p.tables.add(mask.data(),mask.size()*sizeof(unsigned));
-      p.i_dw=p.tables.add(dw.data(),dw.size()*sizeof(double));
-      p.i_dwq=p.tables.add(dwq.data(),dwq.size()*sizeof(double));
+      build_vertical_pass_plan(v,table);
+      p.tiles=v.tiles;
+      p.kmax=v.kmax;
+      p.i_lo=add(v.lo);
+      p.i_rows=add(v.rows);
+      p.i_mask=add(v.mask);
+      p.i_dw=add(v.w);
+      p.i_dwq=add(v.wq);
     }
   else
     {
-      // widest source span of any 256-column tile decides how many rows fit in LDS
-      int max_span=1;
-      for (int x0=0; x0 < table.out_size; x0+=256)
-        {
-          int xh=(x0+255) < table.out_size ? (x0+255) : table.out_size-1;
-          int l=table.start[(size_t) x0],hi=0;
-          for (int i=x0; i <= xh; i++)
-            {
-              int st=table.start[(size_t) i],e=st+table.count[(size_t) i];
-              l=st < l ? st : l;
-              hi=e > hi ? e : hi;
-            }
-          if (hi < l)
-            hi=l;
-          tile_lo.push_back(l);
-          tile_span.push_back(hi-l);
-          if ((hi-l) > max_span)
-            max_span=hi-l;
-        }
-      // per tile: the largest tap count (run by every lane of the converted-tile kernel)
-      const size_t ntiles=tile_lo.size();
-      // (a 4x Lanczos enlargement has 6 or 7 contributions per output: 7 taps, not 8)
-      const int maxt=table.max_taps <= 4 ? 4 : (table.max_taps <= 6 ? 6 : (table.max_taps <= 7 ? 7 : 8));
-      int overhang=0;
-      for (size_t t=0; t < ntiles; t++)
-        {
-          int x0t=(int) t*256,xh=(x0t+255) < table.out_size ? (x0t+255) : table.out_size-1;
-          int cmaxt=0,endmax=0;
-          for (int i=x0t; i <= xh; i++)
-            cmaxt=table.count[(size_t) i] > cmaxt ? table.count[(size_t) i] : cmaxt;
-          for (int i=x0t; i <= xh; i++)
-            {
-              int e=table.start[(size_t) i]+maxt;       // the kernel reads MAXT samples per output
-              endmax=e > endmax ? e : endmax;
-            }
-          int over=endmax-(tile_lo[t]+tile_span[t]);
-          overhang=over > overhang ? over : overhang;
-          tile_span.push_back(cmaxt);                 // second half of the array: taps per tile
-        }
-      p.max_span=max_span;
-      p.overhang=overhang;
-      p.maxt=maxt;
-      p.i_tile_lo=p.tables.add(tile_lo.data(),tile_lo.size()*sizeof(int));
-      p.i_tile_span=p.tables.add(tile_span.data(),tile_span.size()*sizeof(int));
+      build_horizontal_pass_plan(h,table);
+      p.spans=h;
+      p.i_start=add(table.start);
+      p.i_w=add(table.weight);
+      p.i_wq=add(h.wq);
+      p.i_tile_lo=add(h.tile_lo);
+      p.i_tile_span=add(h.tile_span);
     }
-  MH_TRY(p.tables.upload(device,stream));
-  p.device=device;
-  MH_HIP(hipEventCreateWithFlags(&p.ready,hipEventDisableTiming));
-  MH_HIP(hipEventRecord(p.ready,stream));
-  return MH_OK;
+  return p.publish(device,stream);
 }
 
 // cached by the serial number of a shared contribution table (resize_filter.cpp); tables built
 // for one call (serial 0: the MagickCore shim's callback filters) are not kept
-struct PassTablesEntry { unsigned long long serial; int device; bool vertical; size_t weight_bytes; std::shared_ptr<PassTables> tables; };
-// (never destroyed: at process exit the runtime the device blocks belong to may be gone)
-static std::mutex &pass_tables_lock() { static std::mutex &m=*new std::mutex; return m; }
-static std::vector<PassTablesEntry> &pass_tables() { static std::vector<PassTablesEntry> &v=*new std::vector<PassTablesEntry>; return v; }
+struct PassKey
+{
+  unsigned long long serial; int device; bool vertical;
+  bool operator==(const PassKey &o) const { return (serial == o.serial) && (device == o.device) && (vertical == o.vertical); }
+};
+typedef MruCache<PassKey,std::shared_ptr<PassTables>> PassCache;
+static PassCache &pass_cache() { static PassCache &c=*new PassCache(8); return c; }
 
 void release_resize_tables()
 {
-  std::lock_guard<std::mutex> guard(pass_tables_lock());
-  pass_tables().clear();
+  auto released=pass_cache().clear();
+  release_resize_stream_plans();
+  release_resize_mfma_plans();
 }
 
-template<typename T>
 static MhStatus acquire_pass_tables(std::shared_ptr<PassTables> *out,const TapTable &table,bool vertical,
-  int device,hipStream_t stream)
+  const View &src)
 {
-  typedef PassTablesEntry Entry;
-  std::mutex &lock=pass_tables_lock();
-  std::vector<Entry> &entries=pass_tables();
-  constexpr size_t kEntries=8;
-  if (table.serial != 0)
-    {
-      std::lock_guard<std::mutex> guard(lock);
-      for (size_t i=0; i < entries.size(); i++)
-        if ((entries[i].serial == table.serial) && (entries[i].device == device) &&
-            (entries[i].vertical == vertical) && (entries[i].weight_bytes == sizeof(T)))
-          {
-            Entry hit=entries[i];
-            entries.erase(entries.begin()+(ptrdiff_t) i);
-            entries.insert(entries.begin(),hit);
-            *out=hit.tables;
-            MH_HIP(hipStreamWaitEvent(stream,hit.tables->ready,0));
-            return MH_OK;
-          }
-    }
-  auto built=std::make_shared<PassTables>();
-  MH_TRY(build_pass_tables<T>(*built,table,vertical,device,stream));
-  *out=built;
-  if (table.serial != 0)
-    {
-      std::lock_guard<std::mutex> guard(lock);
-      entries.insert(entries.begin(),Entry{table.serial,device,vertical,sizeof(T),built});
-      if (entries.size() > kEntries)
-        entries.pop_back();
-    }
-  return MH_OK;
+  return acquire_device_tables(pass_cache(),PassKey{table.serial,src.device,vertical},table.serial != 0,src.stream,out,
+    [&](PassTables &p) { return build_pass_tables(p,table,vertical,src.device,src.stream); });
 }
 
-template<typename Q,int C,bool BLEND,class A>
-static MhStatus launch_typed(const View &src,const View &dst,bool vertical,
-  const TapTable &table,const Roles &roles)
+// f(Layout<Q,C,BLEND>{},A{}) with the frame's layout and the arithmetic policy A of the pass.
+//
+// Both precision modes resample in fp64.  A two-pass resize hands a
+// Quantum-rounded intermediate to the second pass, and with alpha-weighted
+// channels a +-1 difference in a small intermediate alpha moves the final colour
+// by many levels (measured: 15 levels on uniform-random alpha), so an f32 first
+// pass cannot keep the +-1 contract.  FAST selects the fused-multiply-add fp64
+// policy (Fma64), whose intermediate differs from the CPU's only when a value
+// lies within ~1e-11 of a rounding boundary.
+// (operators.cpp hands FAST to the SECOND filter only: the first one's result is rounded and
+// feeds it.)  Alpha-weighted channels keep the reference's order in the second filter too: where
+// the alpha sum cancels to nearly nothing the quotient — or PerceptibleReciprocal's clamp, a
+// factor of 1.5e7 — turns the last bits of the sums into whole levels, and these kernels have no
+// way back to the taps of a single output (the one-launch forms recompute such rows).  So
+// <BLEND = true,Fma64> is never instantiated.
+template<class F>
+static MhStatus dispatch_pass(const View &src,const Roles &roles,MhPrecision prec,F &&f)
 {
-  typedef typename A::T T;
-  std::shared_ptr<PassTables> pass;
-  MH_TRY(acquire_pass_tables<T>(&pass,table,vertical,src.device,src.stream));
-  const TableBundle &tables=pass->tables;
+  const bool fast=(prec == MH_PRECISION_FAST) && !roles.blend;
+  return dispatch_layout_blend(src.quantum,src.channels,roles.blend,[&](auto L)
+  {
+    if constexpr (!decltype(L)::BLEND)
+      {
+        if (fast)
+          return f(L,Fma64{});
+      }
+    return f(L,Exact64{});
+  });
+}
 
+// f(n) with the compile-time n.value = maxt, which is one of N...
+template<int... N,class F>
+static MhStatus dispatch_taps(int maxt,F &&f)
+{
+  MhStatus status=MH_OK;
+  const bool found=(((maxt == N) && ((status=f(std::integral_constant<int,N>{})),true)) || ...);
+  return found ? status : fail(MH_BAD_ARGUMENT,"resize: no kernel of %d taps",maxt);
+}
+
+static MhStatus launch_vertical(const View &src,const View &dst,const TapTable &table,const Roles &roles,
+  MhPrecision prec)
+{
+  std::shared_ptr<PassTables> pass;
+  MH_TRY(acquire_pass_tables(&pass,table,true,src));
+  const TableBundle &tables=pass->tables;
+  VerticalDenseArgs va;
+  va.src=src.pixels;
+  va.dst=dst.pixels;
+  va.columns=(int) dst.columns;
+  va.out_rows=table.out_size;
+  va.kmax=pass->kmax;
+  va.tile_lo=tables.at<int>(pass->i_lo);
+  va.tile_rows=tables.at<int>(pass->i_rows);
+  va.row_mask=tables.at<unsigned>(pass->i_mask);
+  va.w=tables.at<double>(pass->i_dw);
+  va.wq=tables.at<double>(pass->i_dwq);
+  va.nearest=tables.at<int>(pass->i_near);
+  va.count=tables.at<int>(pass->i_count);
+  va.copy_mask=roles.copy_mask;
+  const dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) pass->tiles);
+  ProfileScope prof("resize_vertical",src.stream);
+  return dispatch_pass(src,roles,prec,[&](auto L,auto policy)
+  {
+    using Q=typename decltype(L)::Q;
+    using A=decltype(policy);
+    return launch_dynamic_lds(&resize_vertical_kernel<Q,L.C,L.BLEND,A,kVerticalRows>,grid,dim3(256),0,src.stream,va);
+  });
+}
+
+static MhStatus launch_horizontal(const View &src,const View &dst,const TapTable &table,const Roles &roles,
+  MhPrecision prec)
+{
+  std::shared_ptr<PassTables> pass;
+  MH_TRY(acquire_pass_tables(&pass,table,false,src));
+  const TableBundle &tables=pass->tables;
   ResizeArgs args;
   args.src=src.pixels;
   args.dst=dst.pixels;
@@ -688,147 +601,34 @@ static MhStatus launch_typed(const View &src,const View &dst,bool vertical,
   args.nearest=tables.at<int>(pass->i_near);
   args.weight=tables.at<void>(pass->i_w);
   args.weight_qs=tables.at<void>(pass->i_wq);
-  args.tile_lo=nullptr;
-  args.tile_span=nullptr;
-
-  if (vertical)
-    {
-      VerticalDenseArgs va;
-      va.src=src.pixels;
-      va.dst=dst.pixels;
-      va.columns=(int) dst.columns;
-      va.out_rows=table.out_size;
-      va.kmax=pass->kmax;
-      va.tile_lo=tables.at<int>(pass->i_lo);
-      va.tile_rows=tables.at<int>(pass->i_rows);
-      va.row_mask=tables.at<unsigned>(pass->i_mask);
-      va.w=tables.at<double>(pass->i_dw);
-      va.wq=tables.at<double>(pass->i_dwq);
-      va.nearest=tables.at<int>(pass->i_near);
-      va.count=tables.at<int>(pass->i_count);
-      va.copy_mask=roles.copy_mask;
-      dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) pass->tiles);
-      ProfileScope prof("resize_vertical",src.stream);
-      hipLaunchKernelGGL((resize_vertical_kernel<Q,C,BLEND,A,kVerticalRows>),grid,dim3(256),0,src.stream,va);
-    }
-  else
-    {
-      const int max_span=pass->max_span,overhang=pass->overhang,maxt=pass->maxt;
-      args.tile_lo=tables.at<int>(pass->i_tile_lo);
-      args.tile_span=tables.at<int>(pass->i_tile_span);
-      const size_t px=(size_t) C*sizeof(Q);
-      const size_t budget=60u*1024u;
-      if (table.max_taps <= 8)
-        {
-          const int lds_span=max_span+overhang;
-          const size_t cpx=(size_t) C*sizeof(T);
-          if ((size_t) lds_span*cpx <= 150u*1024u)
-            {
-              int tile_rows=(int) (budget/((size_t) lds_span*cpx));
-              tile_rows=tile_rows < 1 ? 1 : (tile_rows > 16 ? 16 : tile_rows);
-              size_t lds=(size_t) lds_span*cpx*(size_t) tile_rows;
-              dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) ((dst.rows+tile_rows-1)/tile_rows));
-              ProfileScope prof("resize_horizontal",src.stream);
-              constexpr bool kCanPremultiply=ResizeAcc<Q,C,BLEND,A>::kDerive;
-              const bool premultiply=kCanPremultiply && (args.copy_mask == 0);
-#define MH_LAUNCH_H(N)                                                                        \
-              {                                                                                \
-                if (premultiply)                                                               \
-                  {                                                                            \
-                    if (lds > 64u*1024u)                                                       \
-                      MH_HIP(hipFuncSetAttribute(                                              \
-                        reinterpret_cast<const void *>(&resize_horizontal_cvt_kernel<Q,C,BLEND,A,N,kCanPremultiply>),\
-                        hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));                \
-                    hipLaunchKernelGGL((resize_horizontal_cvt_kernel<Q,C,BLEND,A,N,kCanPremultiply>),grid,dim3(256),lds, \
-                      src.stream,args,tile_rows,lds_span);                                     \
-                  }                                                                            \
-                else                                                                           \
-                  {                                                                            \
-                    if (lds > 64u*1024u)                                                       \
-                      MH_HIP(hipFuncSetAttribute(                                              \
-                        reinterpret_cast<const void *>(&resize_horizontal_cvt_kernel<Q,C,BLEND,A,N>),\
-                        hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));                \
-                    hipLaunchKernelGGL((resize_horizontal_cvt_kernel<Q,C,BLEND,A,N>),grid,dim3(256),lds, \
-                      src.stream,args,tile_rows,lds_span);                                     \
-                  }                                                                            \
-              }
-              if (maxt == 4) MH_LAUNCH_H(4)
-              else if (maxt == 6) MH_LAUNCH_H(6)
-              else if (maxt == 7) MH_LAUNCH_H(7)
-              else MH_LAUNCH_H(8)
-#undef MH_LAUNCH_H
-              MH_HIP(hipGetLastError());
-              return MH_OK;
-            }
-        }
-      if ((size_t) max_span*px > 150u*1024u)
-        return fail(MH_UNSUPPORTED,"resize: source span of %d pixels does not fit LDS",max_span);
-      int tile_rows=(int) (budget/((size_t) max_span*px));
-      tile_rows=tile_rows < 1 ? 1 : (tile_rows > 16 ? 16 : tile_rows);
-      size_t lds=(size_t) max_span*px*(size_t) tile_rows;
-      dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) ((dst.rows+tile_rows-1)/tile_rows));
-      ProfileScope prof("resize_horizontal",src.stream);
-      if (table.max_taps <= 8)
-        {
-          if (lds > 64u*1024u)
-            MH_HIP(hipFuncSetAttribute(
-              reinterpret_cast<const void *>(&resize_horizontal_kernel<Q,C,BLEND,A,8>),
-              hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
-          hipLaunchKernelGGL((resize_horizontal_kernel<Q,C,BLEND,A,8>),grid,dim3(256),lds,
-            src.stream,args,tile_rows);
-        }
-      else if (table.max_taps <= 16)
-        {
-          // reductions (2x .. 2.6x Lanczos): the lane's weights in registers across the tile's rows
-          if (lds > 64u*1024u)
-            MH_HIP(hipFuncSetAttribute(
-              reinterpret_cast<const void *>(&resize_horizontal_kernel<Q,C,BLEND,A,16>),
-              hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
-          hipLaunchKernelGGL((resize_horizontal_kernel<Q,C,BLEND,A,16>),grid,dim3(256),lds,
-            src.stream,args,tile_rows);
-        }
-      else if (table.max_taps <= 32)
-        {
-          // ... up to 5x (a 4x Lanczos reduction: 25 contributions per output)
-          if (lds > 64u*1024u)
-            MH_HIP(hipFuncSetAttribute(
-              reinterpret_cast<const void *>(&resize_horizontal_kernel<Q,C,BLEND,A,32>),
-              hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
-          hipLaunchKernelGGL((resize_horizontal_kernel<Q,C,BLEND,A,32>),grid,dim3(256),lds,
-            src.stream,args,tile_rows);
-        }
-      else
-        {
-          if (lds > 64u*1024u)
-            MH_HIP(hipFuncSetAttribute(
-              reinterpret_cast<const void *>(&resize_horizontal_kernel<Q,C,BLEND,A,0>),
-              hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
-          hipLaunchKernelGGL((resize_horizontal_kernel<Q,C,BLEND,A,0>),grid,dim3(256),lds,
-            src.stream,args,tile_rows);
-        }
-    }
-  MH_HIP(hipGetLastError());
-  return MH_OK;
-}
-
-template<typename Q,class A>
-static MhStatus dispatch(const View &src,const View &dst,bool vertical,const TapTable &table,
-  const Roles &roles)
-{
-  const bool blend=roles.blend && (roles.alpha == src.channels-1);
-  switch (src.channels)
+  args.tile_lo=tables.at<int>(pass->i_tile_lo);
+  args.tile_span=tables.at<int>(pass->i_tile_span);
+  const HorizontalLaunch g=horizontal_launch(pass->spans,table.max_taps,src.channels,
+    src.quantum == MH_QUANTUM_U16 ? sizeof(uint16_t) : sizeof(float));
+  if (!g.fits)
+    return fail(MH_UNSUPPORTED,"resize: source span of %d pixels does not fit LDS",pass->spans.max_span);
+  const dim3 grid((unsigned) ((dst.columns+255)/256),(unsigned) ((dst.rows+g.tile_rows-1)/g.tile_rows));
+  ProfileScope prof("resize_horizontal",src.stream);
+  return dispatch_pass(src,roles,prec,[&](auto L,auto policy)
   {
-    case 1: return launch_typed<Q,1,false,A>(src,dst,vertical,table,roles);
-    case 2:
-      if (blend) return launch_typed<Q,2,true,A>(src,dst,vertical,table,roles);
-      return launch_typed<Q,2,false,A>(src,dst,vertical,table,roles);
-    case 3: return launch_typed<Q,3,false,A>(src,dst,vertical,table,roles);
-    case 4:
-      if (blend) return launch_typed<Q,4,true,A>(src,dst,vertical,table,roles);
-      return launch_typed<Q,4,false,A>(src,dst,vertical,table,roles);
-    default: break;
-  }
-  return fail(MH_UNSUPPORTED,"%d channels",src.channels);
+    using Q=typename decltype(L)::Q;
+    using A=decltype(policy);
+    constexpr int C=decltype(L)::C;
+    constexpr bool BLEND=decltype(L)::BLEND;
+    if (g.converted)
+      return dispatch_taps<4,6,7,8>(g.maxt,[&](auto n)
+      {
+        return launch_dynamic_lds(&resize_horizontal_cvt_kernel<Q,C,BLEND,A,n.value>,grid,dim3(256),g.lds,src.stream,
+          args,g.tile_rows,g.lds_span);
+      });
+    // (16: reductions, 2x .. 2.6x Lanczos, the lane's weights in registers across the tile's rows; 32: up to 5x — a
+    // 4x Lanczos reduction has 25 contributions per output; 0: any number)
+    return dispatch_taps<8,16,32,0>(g.maxt,[&](auto n)
+    {
+      return launch_dynamic_lds(&resize_horizontal_kernel<Q,C,BLEND,A,n.value>,grid,dim3(256),g.lds,src.stream,args,
+        g.tile_rows);
+    });
+  });
 }
 
 MhStatus launch_resize_pass(const View &src,const View &dst,bool vertical,
@@ -841,27 +641,10 @@ MhStatus launch_resize_pass(const View &src,const View &dst,bool vertical,
     return fail(MH_BAD_ARGUMENT,"resize: geometry mismatch");
   if (roles.blend && (roles.alpha != src.channels-1))
     return fail(MH_UNSUPPORTED,"alpha channel must be the last channel");
-  // Both precision modes resample in fp64.  A two-pass resize hands a
-  // Quantum-rounded intermediate to the second pass, and with alpha-weighted
-  // channels a +-1 difference in a small intermediate alpha moves the final colour
-  // by many levels (measured: 15 levels on uniform-random alpha), so an f32 first
-  // pass cannot keep the +-1 contract.  FAST selects the fused-multiply-add fp64
-  // policy (Fma64), whose intermediate differs from the CPU's only when a value
-  // lies within ~1e-11 of a rounding boundary.
-  // (operators.cpp hands FAST to the SECOND filter only: the first one's result is rounded and
-  // feeds it.)  Alpha-weighted channels keep the reference's order in the second filter too: where
-  // the alpha sum cancels to nearly nothing the quotient — or PerceptibleReciprocal's clamp, a
-  // factor of 1.5e7 — turns the last bits of the sums into whole levels, and these kernels have no
-  // way back to the taps of a single output (the one-launch forms recompute such rows).
-  if ((prec == MH_PRECISION_FAST) && !(roles.blend && (roles.alpha == src.channels-1)))
-    {
-      if (src.quantum == MH_QUANTUM_U16)
-        return dispatch<uint16_t,Fma64>(src,dst,vertical,table,roles);
-      return dispatch<float,Fma64>(src,dst,vertical,table,roles);
-    }
-  if (src.quantum == MH_QUANTUM_U16)
-    return dispatch<uint16_t,Exact64>(src,dst,vertical,table,roles);
-  return dispatch<float,Exact64>(src,dst,vertical,table,roles);
+  // (dispatch_layout_blend sends every other channel count to 4)
+  if ((src.channels < 1) || (src.channels > 4))
+    return fail(MH_UNSUPPORTED,"%d channels",src.channels);
+  return vertical ? launch_vertical(src,dst,table,roles,prec) : launch_horizontal(src,dst,table,roles,prec);
 }
 
 } // namespace mh

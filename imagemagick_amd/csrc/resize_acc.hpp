@@ -74,16 +74,6 @@ struct ResizeAcc
           s[c]=A::mac(s[c],w,p[c]);
       }
   }
-  // kDerive with a sample staged as (alpha*p .., alpha): sum w*(alpha*p) instead of
-  // sum (w*alpha)*p — one fused multiply-add per channel and tap, no product per tap (the staging
-  // pays the three products once per SOURCE sample, which ~4*taps outputs share)
-  __device__ __forceinline__ void tap_premultiplied(T w,const T (&p)[C])
-  {
-    static_assert(kDerive,"the premultiplied form is the derived-gamma mode's");
-#pragma unroll
-    for (int c=0; c < C; c++)
-      s[c]=A::mac(s[c],w,p[c]);
-  }
   __device__ __forceinline__ void finish(const Q (&copy)[C],uint32_t copy_mask,Q (&out)[C]) const
   {
     if constexpr (kDerive)

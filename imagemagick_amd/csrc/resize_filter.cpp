@@ -6,10 +6,10 @@
 // the reference's operation order: the weights these functions return are
 // compared bit-for-bit with the compiled reference in tests/.
 #include "resize_filter.hpp"
+#include "mru_cache.hpp"
 #include <cstring>
 #include <memory>
 #include <atomic>
-#include <mutex>
 #include <thread>
 
 #include <cmath>
@@ -381,13 +381,8 @@ struct TapKey
   size_t in_size,out_size;
   bool operator==(const TapKey &o) const { return memcmp(this,&o,sizeof(TapKey)) == 0; }
 };
-struct TapCache
-{
-  std::mutex lock;
-  std::vector<std::pair<TapKey,std::shared_ptr<const TapTable>>> entries;   // front = most recent
-};
-TapCache &tap_cache() { static TapCache *c=new TapCache(); return *c; }
-constexpr size_t kTapCacheEntries=8;
+typedef MruCache<TapKey,std::shared_ptr<const TapTable>> TapCache;
+TapCache &tap_cache() { static TapCache *c=new TapCache(8); return *c; }
 }
 
 std::shared_ptr<const TapTable> acquire_tap_table(const MhResizeFilter *filter,size_t in_size,
@@ -412,26 +407,13 @@ std::shared_ptr<const TapTable> acquire_tap_table(const MhResizeFilter *filter,s
   key.factor=factor;
   key.in_size=in_size;
   key.out_size=out_size;
-  TapCache &cache=tap_cache();
-  {
-    std::lock_guard<std::mutex> guard(cache.lock);
-    for (size_t i=0; i < cache.entries.size(); i++)
-      if (cache.entries[i].first == key)
-        {
-          auto hit=cache.entries[i];
-          cache.entries.erase(cache.entries.begin()+(ptrdiff_t) i);
-          cache.entries.insert(cache.entries.begin(),hit);
-          return hit.second;
-        }
-  }
+  if (auto hit=tap_cache().find(key))
+    return hit;
   auto table=std::make_shared<TapTable>();
   build_tap_table(*table,filter,in_size,out_size,factor);
   static std::atomic<unsigned long long> next_serial{1};
   table->serial=next_serial.fetch_add(1);
-  std::lock_guard<std::mutex> guard(cache.lock);
-  cache.entries.insert(cache.entries.begin(),{key,table});
-  if (cache.entries.size() > kTapCacheEntries)
-    cache.entries.pop_back();
+  auto evicted=tap_cache().insert(key,table);     // let go of on return, outside the cache's lock
   return table;
 }
 

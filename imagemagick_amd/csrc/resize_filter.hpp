@@ -46,4 +46,20 @@ void build_tap_table(TapTable &table,const MhResizeFilter *filter,size_t in_size
 std::shared_ptr<const TapTable> acquire_tap_table(const MhResizeFilter *filter,size_t in_size,
   size_t out_size,double factor);
 
+// What the launchers of a whole resize (both filters in one call: launch_resize_fused,
+// launch_resize_stream, launch_resize_mfma) look at first, in this order.  Each has its own answer
+// to a finding: an error, or a decline that leaves the frame to the two passes.
+enum ResizeFront { RESIZE_FRONT_OK=0,RESIZE_FRONT_LAYOUT,RESIZE_FRONT_ALPHA_NOT_LAST,RESIZE_FRONT_GEOMETRY };
+static inline ResizeFront resize_front_check(const View &src,const View &dst,const TapTable &vertical,
+  const TapTable &horizontal,const Roles &roles)
+{
+  if ((src.channels != dst.channels) || (src.quantum != dst.quantum))
+    return RESIZE_FRONT_LAYOUT;
+  if (roles.blend && (roles.alpha != src.channels-1))
+    return RESIZE_FRONT_ALPHA_NOT_LAST;
+  if (((int) dst.rows != vertical.out_size) || ((int) dst.columns != horizontal.out_size))
+    return RESIZE_FRONT_GEOMETRY;
+  return RESIZE_FRONT_OK;
+}
+
 } // namespace mh

@@ -36,10 +36,11 @@
 #include "mh_internal.hpp"
 #include "resize_filter.hpp"
 #include "resize_mfma_plan.hpp"
+#include "layout_dispatch.hpp"
+#include "mru_cache.hpp"
 #include "device_common.hpp"
 #include "resize_acc.hpp"
 #include <memory>
-#include <mutex>
 
 namespace mh {
 
@@ -384,39 +385,26 @@ void resize_mfma_kernel(MfmaResizeArgs a)
 }
 
 // ------------------------------------------------------------------ host side
-struct MfmaPlanDevice
+struct MfmaPlanDevice : DeviceTables
 {
   MfmaResizePlan plan;
-  TableBundle tables;
   size_t i_col_lo=0,i_nvb=0,i_wbase=0,i_wcount=0,i_meta=0,i_wh=0;
   size_t i_row_lo=0,i_nvk=0,i_rwoff=0,i_wv=0,i_vstart=0,i_vcount=0,i_hstart=0,i_hcount=0,i_vw=0,i_hw=0;
-  hipEvent_t ready=nullptr;
-  int device=-1;
   bool ok=false;
-  ~MfmaPlanDevice()
-  {
-    if (device >= 0)
-      {
-        DeviceGuard guard;
-        if (guard.enter(device) == hipSuccess)
-          (void) hipDeviceSynchronize();     // shared across streams, as PassTables (resize.hip)
-      }
-    if (ready != nullptr)
-      (void) hipEventDestroy(ready);
-  }
 };
 
-struct MfmaPlanEntry
+struct MfmaPlanKey
 {
-  unsigned long long vserial,hserial; int device,tps; std::shared_ptr<MfmaPlanDevice> plan;
+  unsigned long long vserial,hserial; int device,tps;
+  bool operator==(const MfmaPlanKey &o) const
+  { return (vserial == o.vserial) && (hserial == o.hserial) && (device == o.device) && (tps == o.tps); }
 };
-static std::mutex &mfma_plans_lock() { static std::mutex &m=*new std::mutex; return m; }
-static std::vector<MfmaPlanEntry> &mfma_plans() { static std::vector<MfmaPlanEntry> &v=*new std::vector<MfmaPlanEntry>; return v; }
+typedef MruCache<MfmaPlanKey,std::shared_ptr<MfmaPlanDevice>> MfmaPlanCache;
+static MfmaPlanCache &mfma_plans() { static MfmaPlanCache &c=*new MfmaPlanCache(16); return c; }
 
 void release_resize_mfma_plans()
 {
-  std::lock_guard<std::mutex> guard(mfma_plans_lock());
-  mfma_plans().clear();
+  auto released=mfma_plans().clear();
 }
 
 // Four waves a workgroup: three workgroups = three waves a SIMD fit a CU's LDS (weights 24 KB + patch 29 KB each for
@@ -437,10 +425,7 @@ static MhStatus build_plan_device(MfmaPlanDevice &d,const TapTable &vt,const Tap
   d.i_vstart=MH_ADD(vt.start); d.i_vcount=MH_ADD(vt.count); d.i_hstart=MH_ADD(ht.start); d.i_hcount=MH_ADD(ht.count);
   d.i_vw=MH_ADD(vt.weight); d.i_hw=MH_ADD(ht.weight);
 #undef MH_ADD
-  MH_TRY(d.tables.upload(device,stream));
-  d.device=device;
-  MH_HIP(hipEventCreateWithFlags(&d.ready,hipEventDisableTiming));
-  MH_HIP(hipEventRecord(d.ready,stream));
+  MH_TRY(d.publish(device,stream));
   // the weight blocks are only read by the kernel: free the host copies
   d.plan.wh.clear(); d.plan.wh.shrink_to_fit();
   d.plan.wv.clear(); d.plan.wv.shrink_to_fit();
@@ -448,44 +433,11 @@ static MhStatus build_plan_device(MfmaPlanDevice &d,const TapTable &vt,const Tap
 }
 
 static MhStatus acquire_plan(std::shared_ptr<MfmaPlanDevice> *out,const TapTable &vt,const TapTable &ht,int tps,
-  int device,hipStream_t stream)
+  const View &src)
 {
-  const bool shared=(vt.serial != 0) && (ht.serial != 0);
-  constexpr size_t kEntries=16;
-  if (shared)
-    {
-      std::lock_guard<std::mutex> guard(mfma_plans_lock());
-      std::vector<MfmaPlanEntry> &entries=mfma_plans();
-      for (size_t i=0; i < entries.size(); i++)
-        if ((entries[i].vserial == vt.serial) && (entries[i].hserial == ht.serial) &&
-            (entries[i].device == device) && (entries[i].tps == tps))
-          {
-            MfmaPlanEntry hit=entries[i];
-            entries.erase(entries.begin()+(ptrdiff_t) i);
-            entries.insert(entries.begin(),hit);
-            *out=hit.plan;
-            if (hit.plan->ok)
-              MH_HIP(hipStreamWaitEvent(stream,hit.plan->ready,0));
-            return MH_OK;
-          }
-    }
-  auto built=std::make_shared<MfmaPlanDevice>();
-  MH_TRY(build_plan_device(*built,vt,ht,tps,device,stream));
-  *out=built;
-  // (the evicted plan is released after the lock: its destructor drains the device)
-  std::shared_ptr<MfmaPlanDevice> evicted;
-  if (shared)
-    {
-      std::lock_guard<std::mutex> guard(mfma_plans_lock());
-      std::vector<MfmaPlanEntry> &entries=mfma_plans();
-      entries.insert(entries.begin(),MfmaPlanEntry{vt.serial,ht.serial,device,tps,built});
-      if (entries.size() > kEntries)
-        {
-          evicted=std::move(entries.back().plan);
-          entries.pop_back();
-        }
-    }
-  return MH_OK;
+  return acquire_device_tables(mfma_plans(),MfmaPlanKey{vt.serial,ht.serial,src.device,tps},
+    (vt.serial != 0) && (ht.serial != 0),src.stream,out,[&](MfmaPlanDevice &d)
+    { return build_plan_device(d,vt,ht,tps,src.device,src.stream); });
 }
 
 static size_t mfma_weight_bytes(const MfmaResizePlan &p) { return ((size_t) p.wblocks_max*512u+15u) & ~(size_t) 15u; }
@@ -525,23 +477,15 @@ static MhStatus launch_mfma_typed(const View &src,const View &dst,const MfmaPlan
   const int groups=(p.nrg+WAVES-1)/WAVES;
   const int chunks=(groups+steps-1)/steps;
   dim3 grid((unsigned) (8*a.strips_per_xcd*chunks));
-  if (lds > 64u*1024u)
-    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&resize_mfma_kernel<Q,BLEND,WAVES,NK>),
-      hipFuncAttributeMaxDynamicSharedMemorySize,(int) lds));
   ProfileScope prof("resize_mfma",src.stream);
-  hipLaunchKernelGGL((resize_mfma_kernel<Q,BLEND,WAVES,NK>),grid,dim3(64*WAVES),lds,src.stream,a);
-  MH_HIP(hipGetLastError());
-  return MH_OK;
+  return launch_dynamic_lds(&resize_mfma_kernel<Q,BLEND,WAVES,NK>,grid,dim3(64*WAVES),lds,src.stream,a);
 }
 
 template<int NK>
 static MhStatus launch_mfma_quantum(const View &src,const View &dst,const MfmaPlanDevice &d,int steps,bool blend)
 {
-  if (src.quantum == MH_QUANTUM_U16)
-    return blend ? launch_mfma_typed<uint16_t,true,kMfmaWaves,NK>(src,dst,d,steps) :
-                   launch_mfma_typed<uint16_t,false,kMfmaWaves,NK>(src,dst,d,steps);
-  return blend ? launch_mfma_typed<float,true,kMfmaWaves,NK>(src,dst,d,steps) :
-                 launch_mfma_typed<float,false,kMfmaWaves,NK>(src,dst,d,steps);
+  return dispatch_rgba_blend(src.quantum,blend,[&](auto L)
+    { return launch_mfma_typed<typename decltype(L)::Q,L.BLEND,kMfmaWaves,NK>(src,dst,d,steps); });
 }
 
 static MhStatus launch_mfma_blocks(const View &src,const View &dst,const MfmaPlanDevice &d,int steps,bool blend)
@@ -561,12 +505,13 @@ MhStatus launch_resize_mfma(const View &src,const View &dst,const TapTable &vert
   const Roles &roles,bool *handled)
 {
   *handled=false;
-  if ((src.channels != 4) || (dst.channels != 4) || (src.quantum != dst.quantum) || (roles.copy_mask != 0))
+  if ((src.channels != 4) || (roles.copy_mask != 0))
     return MH_OK;
-  if (roles.blend && (roles.alpha != 3))
-    return MH_OK;
-  if (((int) dst.rows != vertical.out_size) || ((int) dst.columns != horizontal.out_size))
+  const ResizeFront front=resize_front_check(src,dst,vertical,horizontal,roles);
+  if (front == RESIZE_FRONT_GEOMETRY)
     return fail(MH_BAD_ARGUMENT,"resize: geometry mismatch");
+  if (front != RESIZE_FRONT_OK)
+    return MH_OK;
   // enlargements only: a reduction's windows are wider than the two blocks the ring holds
   if ((dst.rows < src.rows) || (dst.columns < src.columns))
     return MH_OK;
@@ -581,7 +526,7 @@ MhStatus launch_resize_mfma(const View &src,const View &dst,const TapTable &vert
   // barely-enlarging geometry's wide patch gets narrower strips)
   for ( ; ; tps/=2)
     {
-      MH_TRY(acquire_plan(&plan,vertical,horizontal,tps,src.device,src.stream));
+      MH_TRY(acquire_plan(&plan,vertical,horizontal,tps,src));
       if (!plan->ok || (plan->plan.nk > 5))
         return MH_OK;
       if ((mfma_lds_bytes(plan->plan) <= 78u*1024u) && (16*plan->plan.nvb_max <= 64*kMfmaWaves))

@@ -42,12 +42,13 @@
 #include "mh_internal.hpp"
 #include "resize_filter.hpp"
 #include "resize_stream_plan.hpp"
+#include "layout_dispatch.hpp"
+#include "mru_cache.hpp"
 #include "device_common.hpp"
 #include "resize_acc.hpp"
 #include <cstdio>
 #include <vector>
 #include <memory>
-#include <mutex>
 #include <type_traits>
 
 namespace mh {
@@ -587,38 +588,25 @@ void resize_stream_kernel(StreamResizeArgs a)
 }
 
 // ------------------------------------------------------------------ host side
-struct StreamPlanDevice
+struct StreamPlanDevice : DeviceTables
 {
   StreamResizePlan plan;
-  TableBundle tables;
   size_t i_first=0,i_count=0,i_strip_hw=0,i_listed=0,i_vbase=0,i_vdense=0,i_vstart=0,i_vcount=0,i_hstart=0,i_hcount=0,i_vw=0,i_hw=0;
-  hipEvent_t ready=nullptr;
-  int device=-1,strips=0;
+  int strips=0;
   bool ok=false;
-  ~StreamPlanDevice()
-  {
-    if (device >= 0)
-      {
-        DeviceGuard guard;
-        if (guard.enter(device) == hipSuccess)
-          (void) hipDeviceSynchronize();     // shared across streams, as PassTables (resize.hip)
-      }
-    if (ready != nullptr)
-      (void) hipEventDestroy(ready);
-  }
 };
 
-struct StreamPlanEntry
+struct StreamPlanKey
 {
-  unsigned long long vserial,hserial; int device; std::shared_ptr<StreamPlanDevice> plan;
+  unsigned long long vserial,hserial; int device;
+  bool operator==(const StreamPlanKey &o) const { return (vserial == o.vserial) && (hserial == o.hserial) && (device == o.device); }
 };
-static std::mutex &stream_plans_lock() { static std::mutex &m=*new std::mutex; return m; }
-static std::vector<StreamPlanEntry> &stream_plans() { static std::vector<StreamPlanEntry> &v=*new std::vector<StreamPlanEntry>; return v; }
+typedef MruCache<StreamPlanKey,std::shared_ptr<StreamPlanDevice>> StreamPlanCache;
+static StreamPlanCache &stream_plans() { static StreamPlanCache &c=*new StreamPlanCache(16); return c; }
 
 void release_resize_stream_plans()
 {
-  std::lock_guard<std::mutex> guard(stream_plans_lock());
-  stream_plans().clear();
+  auto released=stream_plans().clear();
 }
 
 static MhStatus build_stream_plan_device(StreamPlanDevice &d,const TapTable &vt,const TapTable &ht,int src_columns,
@@ -634,10 +622,7 @@ static MhStatus build_stream_plan_device(StreamPlanDevice &d,const TapTable &vt,
   d.i_vstart=MH_ADD(vt.start); d.i_vcount=MH_ADD(vt.count); d.i_hstart=MH_ADD(ht.start); d.i_hcount=MH_ADD(ht.count);
   d.i_vw=MH_ADD(vt.weight); d.i_hw=MH_ADD(ht.weight);
 #undef MH_ADD
-  MH_TRY(d.tables.upload(device,stream));
-  d.device=device;
-  MH_HIP(hipEventCreateWithFlags(&d.ready,hipEventDisableTiming));
-  MH_HIP(hipEventRecord(d.ready,stream));
+  MH_TRY(d.publish(device,stream));
   d.strips=(int) p.strip_first.size();
   d.plan.vdense.clear(); d.plan.vdense.shrink_to_fit();
   d.plan.vbase.clear(); d.plan.vbase.shrink_to_fit();
@@ -645,43 +630,11 @@ static MhStatus build_stream_plan_device(StreamPlanDevice &d,const TapTable &vt,
 }
 
 static MhStatus acquire_stream_plan(std::shared_ptr<StreamPlanDevice> *out,const TapTable &vt,const TapTable &ht,
-  int src_columns,int src_rows,int device,hipStream_t stream)
+  const View &src)
 {
-  const bool shared=(vt.serial != 0) && (ht.serial != 0);
-  constexpr size_t kEntries=16;
-  if (shared)
-    {
-      std::lock_guard<std::mutex> guard(stream_plans_lock());
-      std::vector<StreamPlanEntry> &entries=stream_plans();
-      for (size_t i=0; i < entries.size(); i++)
-        if ((entries[i].vserial == vt.serial) && (entries[i].hserial == ht.serial) && (entries[i].device == device))
-          {
-            StreamPlanEntry hit=entries[i];
-            entries.erase(entries.begin()+(ptrdiff_t) i);
-            entries.insert(entries.begin(),hit);
-            *out=hit.plan;
-            if (hit.plan->ok)
-              MH_HIP(hipStreamWaitEvent(stream,hit.plan->ready,0));
-            return MH_OK;
-          }
-    }
-  auto built=std::make_shared<StreamPlanDevice>();
-  MH_TRY(build_stream_plan_device(*built,vt,ht,src_columns,src_rows,device,stream));
-  *out=built;
-  // (the evicted plan is released after the lock: its destructor drains the device)
-  std::shared_ptr<StreamPlanDevice> evicted;
-  if (shared)
-    {
-      std::lock_guard<std::mutex> guard(stream_plans_lock());
-      std::vector<StreamPlanEntry> &entries=stream_plans();
-      entries.insert(entries.begin(),StreamPlanEntry{vt.serial,ht.serial,device,built});
-      if (entries.size() > kEntries)
-        {
-          evicted=std::move(entries.back().plan);
-          entries.pop_back();
-        }
-    }
-  return MH_OK;
+  return acquire_device_tables(stream_plans(),StreamPlanKey{vt.serial,ht.serial,src.device},
+    (vt.serial != 0) && (ht.serial != 0),src.stream,out,[&](StreamPlanDevice &d)
+    { return build_stream_plan_device(d,vt,ht,(int) src.columns,(int) src.rows,src.device,src.stream); });
 }
 
 template<typename Q,bool BLEND,int F,int NT,int ROWS>
@@ -760,9 +713,8 @@ static MhStatus launch_stream_typed(const View &src,const View &dst,const Stream
 template<int F,int NT,int ROWS>
 static MhStatus launch_stream_layout(const View &src,const View &dst,const StreamPlanDevice &d,bool blend)
 {
-  if (src.quantum == MH_QUANTUM_U16)
-    return blend ? launch_stream_typed<uint16_t,true,F,NT,ROWS>(src,dst,d) : launch_stream_typed<uint16_t,false,F,NT,ROWS>(src,dst,d);
-  return blend ? launch_stream_typed<float,true,F,NT,ROWS>(src,dst,d) : launch_stream_typed<float,false,F,NT,ROWS>(src,dst,d);
+  return dispatch_rgba_blend(src.quantum,blend,[&](auto L)
+    { return launch_stream_typed<typename decltype(L)::Q,L.BLEND,F,NT,ROWS>(src,dst,d); });
 }
 
 template<int F>
@@ -781,12 +733,13 @@ MhStatus launch_resize_stream(const View &src,const View &dst,const TapTable &ve
   const Roles &roles,bool *handled)
 {
   *handled=false;
-  if ((src.channels != 4) || (dst.channels != 4) || (src.quantum != dst.quantum) || (roles.copy_mask != 0))
+  if ((src.channels != 4) || (roles.copy_mask != 0))
     return MH_OK;
-  if (roles.blend && (roles.alpha != 3))
-    return MH_OK;
-  if (((int) dst.rows != vertical.out_size) || ((int) dst.columns != horizontal.out_size))
+  const ResizeFront front=resize_front_check(src,dst,vertical,horizontal,roles);
+  if (front == RESIZE_FRONT_GEOMETRY)
     return fail(MH_BAD_ARGUMENT,"resize: geometry mismatch");
+  if (front != RESIZE_FRONT_OK)
+    return MH_OK;
   if ((dst.rows < src.rows) || (dst.columns < 2*src.columns) || ((dst.columns % src.columns) != 0) ||
       (dst.columns/src.columns > 4))
     return MH_OK;
@@ -794,7 +747,7 @@ MhStatus launch_resize_stream(const View &src,const View &dst,const TapTable &ve
   if ((dst.columns >= (1u << 27)) || (dst.rows >= (1u << 30)))
     return MH_OK;
   std::shared_ptr<StreamPlanDevice> plan;
-  MH_TRY(acquire_stream_plan(&plan,vertical,horizontal,(int) src.columns,(int) src.rows,src.device,src.stream));
+  MH_TRY(acquire_stream_plan(&plan,vertical,horizontal,src));
   if (!plan->ok)
     return MH_OK;
   // a first filter whose sums land exactly on rounding boundaries once in a few values (StreamResizePlan::

@@ -920,8 +920,6 @@ MH_API void MhTerminus(void)
   release_rccl_communicators();
   release_shared_tables();
   release_resize_tables();
-  release_resize_mfma_plans();
-  release_resize_stream_plans();
   pool_trim();
   staging_trim();
   release_color_tables();

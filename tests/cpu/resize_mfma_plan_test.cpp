@@ -207,6 +207,9 @@ int main()
   bad+=run(17,9,16*17,16*9,16,true);        // 16x
   bad+=run(1,1,40,40,16,true);              // one source pixel
   bad+=run(600,23,2400,92,16,true);
+  // the ends of the walk of tests/test_gpu_resize_plan_caches.py: 37x23 to 85 columns, 53 .. 70 rows
+  bad+=run(37,23,85,53,16,true);
+  bad+=run(37,23,85,70,16,true);
   bad+=run(64,100,256,400,16,true,6);       // six waves a workgroup
   bad+=run(53,37,212,148,16,true,6);
   if (bad == 0)

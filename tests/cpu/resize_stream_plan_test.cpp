@@ -184,6 +184,9 @@ int main()
   failures+=check(9,5,36,20,lanczos3,3.0,false,"lanczos 4x, 5 columns");
   failures+=check(7,3,7,6,lanczos3,3.0,false,"lanczos 2x, 3 columns");
   failures+=check(12,58,30,116,lanczos3,3.0,true,"lanczos 2x");
+  // the ends of the walk of tests/test_gpu_resize_plan_caches.py: 37x23 to 74 columns, 46 .. 63 rows
+  failures+=check(23,37,46,74,lanczos3,3.0,true,"lanczos 2x, plan cache walk");
+  failures+=check(23,37,63,74,lanczos3,3.0,true,"lanczos 2x, plan cache walk");
   failures+=check(90,100,180,200,catrom,2.0,true,"catrom 2x");
   // 3x: the middle output of a column sits at whole-number distances (minus MagickEpsilon) from its
   // taps — the zeros of every interpolating filter: weights born of cancellation, 1e-12 +- 1e-15 from

@@ -34,7 +34,7 @@ def max_taps(support, source, destination):
     return max(count for _, count in windows(support, source, destination))
 
 
-# The horizontal kernel is chosen by the largest window of the pass (resize.hip, launch_typed): a tile of
+# The horizontal kernel is chosen by the largest window of the pass (resize_pass_plan.hpp, horizontal_launch): a tile of
 # converted samples with 4, 6, 7 or 8 taps a lane, or the plain tile with 8, 16, 32 or any number.
 TAP_CLASSES = ["<=4", "5-6", "7", "8", "9-16", "17-32", ">32"]
 
