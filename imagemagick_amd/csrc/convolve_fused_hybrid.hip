@@ -618,7 +618,8 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
   //               quotients' weights (alpha_weight)
   //   interval B: f16 row chain of group g (row waves): matrix pipe  ||  colour epilogue of group g-1: f32 sums x
   //               the weights of interval A -> ring slot  ||  alpha waves: group g's byte-plane operands into
-  //               registers  ||  every wave: the store of one of block cb's rows
+  //               registers  ||  every wave: the store of one of block cb's rows (steady state: read at the head of the
+  //               interval and stored from in front of the chain; fill and drain: behind it)
   // What crosses a barrier: a row wave's f32 sums (4 floats); an alpha wave's plane operands (12 registers).
   // (Rounds 4-5 ran the integer chain in interval B and carried its five class tiles across barrier Y: the
   // youngest waves of their SIMDs, the alpha waves issued their 18 matrix instructions behind the 27 of the row
@@ -880,6 +881,12 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
         floatx4 weight;
         if constexpr (BLEND && ROW)
           weight=*reinterpret_cast<const floatx4 *>(alpha_weight+weight_slot(ot));
+        // ... and, steady state, the wave's pixel of out_tile, complete since barrier X: read with the first operand
+        // reads and stored from in front of the chain, so that the round trip to the LDS is not taken behind the chain
+        // and its idle cycles, in front of barrier Y (profiles/hybrid_row_store_waits.md)
+        uintx2 tile_early={0u,0u};
+        if constexpr (STEADY)
+          tile_early=lds_read_at<uintx2>(out_entry);
         if constexpr (BLEND)
           if constexpr (ALPHA)
             {
@@ -894,6 +901,25 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
                 }
             }
         MH_HTRACE_MARK(6);
+        // the store of the column pass's rows, steady state: wave = row of block cb.  The row lies inside the image; its
+        // address is the scalar row base and the lane's offset, the lane's pixel of out_tile a loop-invariant LDS
+        // address (read above)
+        if constexpr (STEADY)
+          {
+            const uint2 result=make_uint2(tile_early[0],tile_early[1]);
+            asm volatile("" : "+s"(destination_rows));             // (as source_rows)
+            auto store_row=[&]()
+            {
+              asm volatile("" : "+v"(dst_entry));                  // (as fetch_steady's offsets)
+              store_pixel16(reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(args.dst)+destination_rows+
+                dst_entry),result);
+            };
+            if constexpr (FULL)
+              store_row();
+            else if (__builtin_amdgcn_inverse_ballot_w64(live_columns))
+              store_row();
+            destination_rows+=group_bytes;
+          }
         // ---- f16 row chain of group g (one channel, 16 rows x 16 columns) and, beside it, the colour epilogue
         // of group g-1: the column pass's samples, UNROUNDED:
         //   alpha-weighted: A*R_c*2^-17 = S_c*weight (the alpha waves' weight, interval A)
@@ -935,27 +961,8 @@ void blur_fused_hybrid_kernel(BlurExactArgs args)
             asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc));
             sums_row=acc;
           }
-        // the store of the column pass's rows: wave = row of block cb
-        // (steady state: the row lies inside the image; its address is the scalar row base and the lane's offset, the
-        // lane's pixel of out_tile a loop-invariant LDS address)
-        if constexpr (STEADY)
-          {
-            const uintx2 tile=lds_read_at<uintx2>(out_entry);
-            const uint2 result=make_uint2(tile[0],tile[1]);
-            asm volatile("" : "+s"(destination_rows));             // (as source_rows)
-            auto store_row=[&]()
-            {
-              asm volatile("" : "+v"(dst_entry));                  // (as fetch_steady's offsets)
-              store_pixel16(reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(args.dst)+destination_rows+
-                dst_entry),result);
-            };
-            if constexpr (FULL)
-              store_row();
-            else if (__builtin_amdgcn_inverse_ballot_w64(live_columns))
-              store_row();
-            destination_rows+=group_bytes;
-          }
-        else if ((cb >= 0) && (cb < nblocks))
+        // ... fill and drain: behind the chain, under the tests of the block and the image's edges
+        if (!STEADY && (cb >= 0) && (cb < nblocks))
           {
             const uintx2 tile=lds_read_at<uintx2>(out_entry);
             const uint2 result=make_uint2(tile[0],tile[1]);
